@@ -2,7 +2,7 @@
 """bench.py -- QP solves/s of the batched CBF-QP filter() hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2..12|qp] [--batch B] [--kernel 100Hz]
-                    [--presolve 1] [--polish 0|1|2] [--no-cpu-baseline] [--no-pcie]
+                    [--presolve 1] [--polish 0|1|2] [--full] [--no-cpu-baseline] [--no-pcie] [--dump-outputs DIR]
                     [--shape c2|c3|c4|c5full] [--lanes 64]       (with --config qp; the realizable filter's 38 x 29 ...
                     86 x 65 and the shipped half-planes' 22 x 15: tools/dev_rz_time.py, tools/scratch/bench_rd22.py)
 
@@ -11,6 +11,11 @@ code) over one batch of synthetic states that is already resident in HBM when th
 `value` is therefore KERNEL-ONLY (inputs and outputs in HBM); the transfer-inclusive rate of SURVEY 8(d)
 (H2D + kernels + D2H of the same batch from host buffers) is reported beside it as `pcie_inclusive`, never as `value`.
 Default workload: BASELINE.json configs[1] -- DoubleIntegrator explicit CBF, batch 65 536 per GPU.
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else -- the CPU baseline and parity
+against the oracle, the PCIe-inclusive leg, the graph replay beside the direct launches, the iteration statistics,
+configs C3 / C4 / C5 and C1 of the default line -- runs only with --full.
+--dump-outputs DIR: after the timed steps, what the last one returned to its caller (rank 0's slice), as DIR/<name>.npy
+in float64; the inputs are seeded, so two builds can be compared output for output.
 N > 1: one process per GPU, the batch axis is sharded -- every rank owns its own slice of the seeded instance
 stream (weak scaling), no data-path collective and no RCCL at all: the barrier around the timed region and the
 max-over-ranks of the elapsed time go over a gloo (TCP, host) process group.  Started by torchrun (RANK / LOCAL_RANK /
@@ -267,6 +272,26 @@ def valu_roofline(sq, step_ms, tag):
                     "gives a SIMD one wave, and a branch instruction costs such a wave 45-55 cycles"}
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array (batch on its last axis) as <path>/<name>.npy in float64 -- the int32 codes are exact
+    in it.  Above DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of batch columns is kept of every array, in
+    increasing order, and its column indices are written as sample_columns.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    B = next(iter(arrays.values())).shape[-1]
+    per_column = sum(a.nbytes for a in arrays.values()) // B
+    if per_column * B > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (per_column + 8)
+        cols = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+        arrays = {k: a[..., cols] for k, a in arrays.items()}
+        arrays["sample_columns"] = cols.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.ascontiguousarray(a))
+
+
 def spawn_ranks(n):
     """--gpus N without a launcher: start the N ranks as fresh child processes (nothing has touched a GPU yet in this
     one), hand them the torchrun environment, pass rank 0's JSON line through."""
@@ -463,6 +488,8 @@ def bench_qp(args, grp, dev):
     step_ms = ms.value / max(args.steps, 1)
     st = status.cpu().numpy()
     it = iters.cpu().numpy()
+    if args.dump_outputs and grp.rank == 0:
+        dump_outputs(args.dump_outputs, {"solution": sol.cpu().numpy(), "status": st, "iterations": it})
     kernel = ("wave-per-QP, plain ADMM (admm_wave.hpp), then qp_inv.hpp / qp_lds.hpp for what it leaves at max_iter"
               if (args.lanes == 64 and solver.polish == 0)
               else "two QPs per wave, K_J^-1 by rank-one steps in registers (qp_inv.hpp)"
@@ -488,7 +515,7 @@ def bench_qp(args, grp, dev):
                         "kernel_avg_us": step_ms * 1e3, "algorithmic_bytes_per_launch": alg * B,
                         "algorithmic_bytes_per_instance": alg, "valu": valu_roofline(sq, step_ms, tag)},
            "cpu_baseline": None}
-    if grp.rank == 0 and grp.world == 1 and not args.no_cpu_baseline:
+    if args.full and grp.rank == 0 and grp.world == 1 and not args.no_cpu_baseline:
         # the oracle as checker + baseline: exact optimum of the same problems (u, delta), OSQP-style ADMM timed
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
@@ -654,18 +681,26 @@ def bench_filter(args, grp, dev, cfg, headline):
     launch_bound = cfg in (2, 11)
     use_graph = args.graph == 1
     elapsed, step_ms, how = timed(use_graph)
+    rc_host = rc.cpu().numpy()
+    if headline and args.dump_outputs and grp.rank == 0:
+        dump_outputs(args.dump_outputs, {"uact": uact.cpu().numpy(), "relax": relax.cpu().numpy(), "rc": rc_host})
     other = None
-    if headline and launch_bound and args.graph < 0:
+    if args.full and headline and launch_bound and args.graph < 0:
         other = timed(True)
 
-    # one extra, untimed call with the diagnostics buffer: ADMM iterations used per instance (last diag row)
-    diag = torch.zeros((d.ndiag, B), dtype=torch.float64, device=dev)
-    capi.check(fn(*(call_args[:8] + (C.c_void_p(diag.data_ptr()), call_args[9]))))
-    torch.cuda.synchronize()
-    iters_host = diag[d.ndiag - 1].cpu().numpy()
-    rc_host = rc.cpu().numpy()
     solved_mask = np.isin(rc_host, (1, 2, -1))
     solved = int(solved_mask.sum())  # instances whose QP was solved (or found infeasible)
+    solver_stats = {"polish": solver.polish}
+    if args.full:
+        # one extra, untimed call with the diagnostics buffer: ADMM iterations used per instance (last diag row)
+        diag = torch.zeros((d.ndiag, B), dtype=torch.float64, device=dev)
+        capi.check(fn(*(call_args[:8] + (C.c_void_p(diag.data_ptr()), call_args[9]))))
+        torch.cuda.synchronize()
+        iters_host = diag[d.ndiag - 1].cpu().numpy()
+        solver_stats.update(
+            admm_iterations_mean=float(iters_host[solved_mask].mean()) if solved else 0.0,
+            admm_iterations_max=float(iters_host[solved_mask].max()) if solved else 0.0,
+            decided_before_first_iteration=float((iters_host[solved_mask] == 0).mean()) if solved else 0.0)
     # "QP solves" counts the instances whose filter() went through a QP (rc 1, 2, -1); TB instances that never reach the
     # backup set (rc -3) are filtered without one and count only in instances_per_s
     solved_all = grp.sum_over_ranks(solved)
@@ -711,10 +746,7 @@ def bench_filter(args, grp, dev, cfg, headline):
                    "launch": how,
                    # how the QPs were decided: polish 2 runs the in-register dual active-set stage first, then OSQP-style
                    # ADMM iterations (with an active-set finish at every check) for what it leaves undecided
-                   "solver": {"polish": solver.polish,
-                              "admm_iterations_mean": float(iters_host[solved_mask].mean()) if solved else 0.0,
-                              "admm_iterations_max": float(iters_host[solved_mask].max()) if solved else 0.0,
-                              "decided_before_first_iteration": float((iters_host[solved_mask] == 0).mean()) if solved else 0.0},
+                   "solver": solver_stats,
                    "rc_histogram": {str(int(k)): int(v) for k, v in zip(*np.unique(rc_host, return_counts=True))},
                    "qp_solved_fraction": solved / B,
                    "value_definition": "kernel-only, inputs and outputs resident in HBM; instances whose filter() solved a "
@@ -741,7 +773,7 @@ def bench_filter(args, grp, dev, cfg, headline):
                                      "kernel_avg_us": ms2 * 1e3, "launch": how2,
                                      "note": "the same K steps captured into one HIP graph before the timed region and "
                                              "replayed once inside it; `value` is the direct-launch figure"}
-    if grp.rank == 0 and grp.world == 1 and not args.no_cpu_baseline:
+    if args.full and grp.rank == 0 and grp.world == 1 and not args.no_cpu_baseline:
         if cfg in (REALIZABLE_CFG, ROBUST_DATA_CFG):
             base, parity = cpu_baseline_handle(cfg, args.kernel if cfg == REALIZABLE_CFG else args.halfplanes,
                                                uact.cpu().numpy(), rc_host, x, udes)
@@ -752,7 +784,7 @@ def bench_filter(args, grp, dev, cfg, headline):
         out["parity"] = parity
     elif grp.rank == 0:
         out["cpu_baseline"] = None
-    if headline and grp.rank == 0 and grp.world == 1 and not args.no_pcie:
+    if args.full and headline and grp.rank == 0 and grp.world == 1 and not args.no_pcie:
         out["pcie_inclusive"] = pcie_inclusive(flt, x, udes, rc_host, uact)
     flt.close()
     return out
@@ -838,7 +870,8 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="all",
-                    help="all (default): C2 is the line's value, C3 / C4 (one GPU's share) / C5 ride in `configs`, C1 in `c1`; "
+                    help="all (default): C2 is the line's value; with --full, C3 / C4 (one GPU's share) / C5 ride in `configs`, "
+                         "C1 in `c1`; "
                          "2..12: one filter config; qp: pre-assembled QPs (see --shape)")
     ap.add_argument("--shape", default="c2", choices=sorted(QP_SHAPES), help="--config qp: which problems")
     ap.add_argument("--batch", type=int, default=0)
@@ -856,12 +889,20 @@ def main():
                          "region) and replayed once inside it -- same K launches, same arguments, same stream order; "
                          "-1 (default): direct launches are `value`, and for the launch-bound explicit filter (config 2, "
                          "11: a launch costs the host 2.8-3.6 us, the kernel runs in about 2) the graph replay of the same "
-                         "K steps is timed too and reported beside it as value_graph_replay")
+                         "K steps is timed too (with --full) and reported beside it as value_graph_replay")
     ap.add_argument("--cpu-seconds", type=float, default=5.0,
                     help="CPU work spent on the cpu_baseline sample of each config in `configs` (the headline's is 15 s)")
     ap.add_argument("--state-scale", type=float, default=1.0,
                     help="multiplies the seeded states (1.0 = the SURVEY 8(d) workload; e.g. 0.5 puts every C2 state inside the "
                          "safe set: no failed instance, the kernel's memory behaviour without the untouched-slot reads)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: CPU baseline + parity against the oracle, the PCIe-inclusive leg, the "
+                         "graph replay of the launch-bound configs, iteration statistics, and for --config all the configs "
+                         "C3 / C4 / C5 and C1 (the --no-* options below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (filter: uact, relax, rc; qp: solution, status, "
+                         "iterations) as DIR/<name>.npy in float64, at most 64 MiB in all (a seeded sample of the batch "
+                         "beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pcie", action="store_true", help="skip the host-buffer (PCIe-inclusive) leg")
     ap.add_argument("--no-c1", action="store_true", help="skip the single-agent C1 leg of --config all")
@@ -885,15 +926,17 @@ def main():
     if args.config != "all":
         out = bench_filter(args, grp, dev, int(args.config), headline=True)
     else:
-        # The line: BASELINE.json configs[1] (C2) is `value`; configs[2..4] -- the pendulum-sized and the 8-GPU one, each
-        # rank its own block (C4: 32 768 per GPU = 262 144 over 8) -- are timed the same way, K steps each between
-        # barriers, and ride in `configs`; configs[0] (single agent, C++ class) in `c1` (rank 0 of a 1-GPU run).
+        # The line: BASELINE.json configs[1] (C2) is `value`; with --full, configs[2..4] -- the pendulum-sized and the
+        # 8-GPU one, each rank its own block (C4: 32 768 per GPU = 262 144 over 8) -- are timed the same way, K steps
+        # each between barriers, and ride in `configs`; configs[0] (single agent, C++ class) in `c1` (rank 0 of a
+        # 1-GPU run).
         out = bench_filter(args, grp, dev, 2, headline=True)
-        out["configs"] = {}
-        for cfg in (3, 4, 5):
-            out["configs"][f"c{cfg}"] = compact(bench_filter(args, grp, dev, cfg, headline=False))
-        if grp.rank == 0 and grp.world == 1 and not args.no_c1 and not args.no_cpu_baseline:
-            out["c1"] = c1_single_agent()
+        if args.full:
+            out["configs"] = {}
+            for cfg in (3, 4, 5):
+                out["configs"][f"c{cfg}"] = compact(bench_filter(args, grp, dev, cfg, headline=False))
+            if grp.rank == 0 and grp.world == 1 and not args.no_c1 and not args.no_cpu_baseline:
+                out["c1"] = c1_single_agent()
     if grp.rank == 0:
         print(json.dumps(out))
     grp.close()

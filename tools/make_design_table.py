@@ -84,7 +84,7 @@ def default_line():
     if not d:
         return ""
     g = d.get("value_graph_replay") or {}
-    out = [f"`python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's command, `profiles/{d['_round']}/default_driver_style_bench.json`): "
+    out = [f"`python bench.py --gpus 1 --steps 20 --warmup 5 --full` (the driver's command with `--full`, `profiles/{d['_round']}/default_driver_style_bench.json`): "
            f"C2 **{fmt_rate(d['value'])} QP solves/s** ({d['ms_per_step'] * 1e3:.2f} µs per step, {d['config']['launch']}; the same 20 steps "
            f"replayed as one HIP graph: {fmt_rate(g.get('value', 0))}/s, {g.get('ms_per_step', 0) * 1e3:.2f} µs), "
            f"`roofline.frac` {d['roofline']['frac']:.3f} (kernel {d['roofline']['kernel_avg_us']:.2f} µs by the run's own event pair), "

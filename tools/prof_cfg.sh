@@ -9,7 +9,7 @@ TAG=$1; shift
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-pcie"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-pcie"
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- $B --steps 200 --warmup 20 "$@" > $OUT/trace.log 2>&1 || echo "trace pass failed"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $B --steps 10 --warmup 2 "$@" > $OUT/pmc_fetch.log 2>&1 || echo "fetch pass failed"
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- $B --steps 10 --warmup 2 "$@" > $OUT/pmc_write.log 2>&1 || echo "write pass failed"

@@ -18,20 +18,20 @@ b)
   bash tools/prof_cfg.sh c2_batch16m --config 2 --batch 16777216 --steps 20 --warmup 3 > /dev/null 2>&1; echo "prof 16m done"
   ;;
 c)
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/default_driver_style_bench.json 2> $O/default.err; echo "driver-style rc $?"
-  timeout -k 10 300 python bench.py > $O/default_bench.json 2>> $O/default.err; echo "default rc $?"
-  for c in 2 3 4 5 6 7 8 9 10 11 12; do timeout -k 10 300 python bench.py --config $c > $O/c${c}_bench.json 2> $O/c${c}_bench.err; echo "config $c rc $?"; done
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/default_driver_style_bench.json 2> $O/default.err; echo "driver-style rc $?"
+  timeout -k 10 300 python bench.py --full > $O/default_bench.json 2>> $O/default.err; echo "default rc $?"
+  for c in 2 3 4 5 6 7 8 9 10 11 12; do timeout -k 10 300 python bench.py --full --config $c > $O/c${c}_bench.json 2> $O/c${c}_bench.err; echo "config $c rc $?"; done
   # the N > 1 path of bench.py on one GPU: four ranks on cuda:0 (the box allows six processes on the card; the 8-rank
   # shard arithmetic is tests/test_sharding_gloo.py, the 8-way split on one device tests/test_gpu_multi.py)
-  ASIF_BENCH_REHEARSAL=1 timeout -k 10 300 python bench.py --gpus 4 --no-cpu-baseline --no-pcie > $O/rehearsal_gpus4_on_one_gpu.json 2> $O/rehearsal.err; echo "rehearsal rc $?"
-  for b in 262144 1048576 4194304 16777216; do timeout -k 10 300 python bench.py --config 2 --batch $b --steps 50 --graph 1 --no-cpu-baseline --no-pcie > $O/c2_batch$b.json 2>/dev/null; done
-  timeout -k 10 300 python bench.py --config 3 --batch 65536 --steps 20 --no-cpu-baseline --no-pcie > $O/c3_batch65536.json 2>/dev/null
-  timeout -k 10 300 python bench.py --config 4 --batch 131072 --steps 20 --no-cpu-baseline --no-pcie > $O/c4_batch131072_fused_pass.json 2>/dev/null
+  ASIF_BENCH_REHEARSAL=1 timeout -k 10 300 python bench.py --full --gpus 4 --no-cpu-baseline --no-pcie > $O/rehearsal_gpus4_on_one_gpu.json 2> $O/rehearsal.err; echo "rehearsal rc $?"
+  for b in 262144 1048576 4194304 16777216; do timeout -k 10 300 python bench.py --full --config 2 --batch $b --steps 50 --graph 1 --no-cpu-baseline --no-pcie > $O/c2_batch$b.json 2>/dev/null; done
+  timeout -k 10 300 python bench.py --full --config 3 --batch 65536 --steps 20 --no-cpu-baseline --no-pcie > $O/c3_batch65536.json 2>/dev/null
+  timeout -k 10 300 python bench.py --full --config 4 --batch 131072 --steps 20 --no-cpu-baseline --no-pcie > $O/c4_batch131072_fused_pass.json 2>/dev/null
   echo "records done"
   ;;
 d)
   for sh in c2 c3 c4 c5full; do bash tools/prof_cfg.sh qp_$sh --config qp --shape $sh > /dev/null 2>&1; echo "prof qp $sh done"; done
-  for sh in c2 c3 c4 c5full; do timeout -k 10 300 python bench.py --config qp --shape $sh > $O/qp_${sh}_bench.json 2>/dev/null; done
+  for sh in c2 c3 c4 c5full; do timeout -k 10 300 python bench.py --full --config qp --shape $sh > $O/qp_${sh}_bench.json 2>/dev/null; done
   timeout -k 10 300 python tools/dev_rz_time.py 100Hz 8 > $O/rz38_time.txt 2>/dev/null
   echo "qp done"
   ;;
