@@ -48,7 +48,7 @@ EXPORTS = [
     "asif_hip_set_learning", "asif_hip_affine_replay", "asif_hip_qp_solve_batch_dense",
     "asif_hip_partition", "asif_hip_create_multi", "asif_hip_multi_destroy", "asif_hip_multi_size",
     "asif_hip_multi_handle", "asif_hip_multi_update_options", "asif_hip_filter_batch_host_multi",
-    "asif_hip_filter_batch_lie",
+    "asif_hip_filter_batch_lie", "asif_hip_filter_vjp_batch",
     "asif_hip_math_probe", "asif_hip_qp_solve_batch_warm",
 ]
 
@@ -166,6 +166,7 @@ def load():
         lib.asif_hip_update_robust_data_options.argtypes = [vp, C.POINTER(RobustDataOptions)]
         lib.asif_hip_rollout_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.asif_hip_set_learning.argtypes = [vp, C.POINTER(LearningData)]
+        lib.asif_hip_filter_vjp_batch.argtypes = [vp, i64, i64] + [vp] * 11
         _lib = lib
     return _lib
 
@@ -250,6 +251,15 @@ class Filter:
         B = x.shape[1]
         check(self.lib.asif_hip_filter_batch_lie(self.handle, B, x.stride(0), _ptr(x), _ptr(udes), _ptr(lfh), _ptr(lgh),
                                                  _ptr(uact), _ptr(relax), _ptr(rc), _ptr(diag), _stream()))
+
+    def filter_vjp(self, x, udes, guact, gudes, rc, lfh=None, lgh=None, glfh=None, glgh=None, gx=None):
+        """The explicit filter backwards (asif_hip_filter_vjp_batch): guact [nu,B] = dL/duAct in; gudes [nu,B] and, with
+        caller-supplied lfh [nc,B], lgh [nc*nu,B], optionally glfh, glgh (same shapes) and gx [nx,B] out; rc int32[B]
+        (1 solved, -1 failed, 0 undecided: gradients 0).  Every tensor shares x's leading dimension."""
+        B = x.shape[1]
+        check(self.lib.asif_hip_filter_vjp_batch(self.handle, B, x.stride(0), _ptr(x), _ptr(udes), _ptr(lfh), _ptr(lgh),
+                                                 _ptr(guact), _ptr(gudes), _ptr(glfh), _ptr(glgh), _ptr(gx), _ptr(rc),
+                                                 _stream()))
 
     def rollout(self, T, dt, x, udes, uact, relax, nfail, xlog=None, ulog=None, rclog=None):
         """T closed-loop steps (filter + plant Euler step) in one launch; x, uact, relax are updated in place."""

@@ -990,6 +990,28 @@ extern "C" int asif_hip_filter_batch_lie(asif_hip_ctx *ctx, int64_t B, int64_t l
 	return run_filter(ctx, a, false, (hipStream_t)stream);
 }
 
+extern "C" int asif_hip_filter_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, const double *udes,
+                                         const double *lfh, const double *lgh, const double *guact, double *gudes,
+                                         double *glfh, double *glgh, double *gx, int32_t *rc, void *stream)
+{
+	if (!ctx || B < 0 || ldx < B || (B > 0 && (!x || !udes || !guact || !gudes || !rc))) return ASIF_HIP_EINVAL;
+	if ((lfh == nullptr) != (lgh == nullptr)) return ASIF_HIP_EINVAL;
+	// the model's own Lie derivatives: their gradient has no caller, and dL/dx would need the model's second derivatives
+	if (!lfh && (glfh || glgh || gx)) return ASIF_HIP_EINVAL;
+	if (ctx->variant != ASIF_HIP_EXPLICIT || ctx->rz || ctx->rb) return ASIF_HIP_EUNSUPPORTED;
+	const asif_hip_solver &S = ctx->solver;
+	// the backward pass repeats the forward pass of the default solver mode (the dual active-set stage) and differentiates
+	// the working set it ends with; the other modes reach the optimum by iterating and hold no working set
+	if (S.polish != 2 || (S.lanes_per_qp != 0 && S.lanes_per_qp != 1)) return ASIF_HIP_EUNSUPPORTED;
+	if (B == 0) return ASIF_HIP_OK;
+	hipError_t e = hipSetDevice(ctx->device);
+	if (e != hipSuccess) return (int)e;
+	const VjpArgs a = {B, ldx, x, udes, lfh, lgh, guact, gudes, glfh, glgh, gx, rc};
+	if (ctx->model == ASIF_HIP_MODEL_DOUBLE_INTEGRATOR) return launch_explicit_vjp_di(ctx->dev, a, (hipStream_t)stream);
+	if (ctx->model == ASIF_HIP_MODEL_PLANAR_TWO_INPUT) return launch_explicit_vjp_p2(ctx->dev, a, (hipStream_t)stream);
+	return ASIF_HIP_EUNSUPPORTED;
+}
+
 extern "C" int asif_hip_rollout_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, double *x,
                                       const double *udes, double *uact, double *relax, int32_t *nfail, double *xlog,
                                       double *ulog, int32_t *rclog, void *stream)

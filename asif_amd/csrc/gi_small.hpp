@@ -36,6 +36,15 @@ constexpr int kGiInfeasible = 2;
 constexpr int kGiUndecided = 0;
 constexpr int kGiFailed = 3; // non-finite problem data: the reference's solver runs such a problem to max_iter
 
+// The working set the method ended with, handed out for the adjoint of the explicit filter (k_explicit_vjp.hip):
+// slot s holds constraint  nrm[s].x >= .  with multiplier lam[s];  id[s] < 0: empty slot (its normal is zero);
+// ids as below: general row r -> r, lower / upper bound of variable j -> GiSmall::kIdLb / kIdUb + j.
+template <int NV>
+struct GiWorkingSet {
+	int id[NV];
+	double lam[NV], nrm[NV][NV];
+};
+
 template <int NV, int RPL, int G>
 struct GiSmall {
 	static_assert(NV >= 1 && NV <= 3, "closed-form working-set solves: nv <= 3");
@@ -94,6 +103,74 @@ struct GiSmall {
 		for (int j = 0; j < NV - 1; j++) x[j < J ? j : j + 1] = xr[j];
 		x[J] = pin;
 		return overflow ? kGiFailed : verdict;
+	}
+
+	// solve_with_pinned, additionally handing out the working set of the REDUCED problem (variable J gone, the others in
+	// their order; general rows keep their ids).  Same arithmetic, same verdicts and optimum as solve_with_pinned: the
+	// forward kernels do not call this entry, the backward kernel of the explicit filter does.
+	template <int J>
+	ASIF_HD static int solve_with_pinned_ws(const QpLaneData<NV, RPL> &in, int g, int max_steps, double (&x)[NV], int &steps,
+	                                        GiWorkingSet<NV - 1> &ws)
+	{
+		static_assert(NV >= 2 && J >= 0 && J < NV, "a variable to eliminate and one to keep");
+		const bool nonfinite = qp_data_nonfinite<NV, RPL, G>(in.Hd, in.c, in.lb, in.ub, in.A, in.b);
+		QpLaneData<NV - 1, RPL> red;
+		const double pin = in.lb[J];
+#pragma unroll
+		for (int k = 0; k < RPL; k++) {
+#pragma unroll
+			for (int j = 0; j < NV - 1; j++) red.A[k][j] = in.A[k][j < J ? j : j + 1];
+			red.b[k] = in.b[k] - in.A[k][J] * pin;
+			red.eq[k] = in.eq[k];
+		}
+#pragma unroll
+		for (int j = 0; j < NV - 1; j++) {
+			const int jj = j < J ? j : j + 1;
+			red.Hd[j] = in.Hd[jj];
+			red.c[j] = in.c[jj];
+			red.lb[j] = in.lb[jj];
+			red.ub[j] = in.ub[jj];
+		}
+		double ovf = 0.0; // as pinned_unchecked
+#pragma unroll
+		for (int k = 0; k < RPL; k++) ovf = fma(red.b[k], 1e160, ovf);
+		const bool overflow = gor<G>(!(fabs(ovf) < __builtin_huge_val()) ? 1 : 0) != 0;
+		double xr[NV - 1];
+		int verdict;
+		if constexpr (NV - 1 == 1) verdict = GiSmall<1, RPL, G>::solve_1d_ws(red, g, xr, steps, ws);
+		else verdict = GiSmall<NV - 1, RPL, G>::template solve_general<true>(red, g, max_steps, xr, steps, &ws);
+#pragma unroll
+		for (int j = 0; j < NV - 1; j++) x[j < J ? j : j + 1] = xr[j];
+		x[J] = pin;
+		return (nonfinite | overflow) ? kGiFailed : verdict;
+	}
+	// solve_1d and the constraint its clip ended on.  The optimum is, bit for bit, the unconstrained minimiser (empty
+	// working set -- also when a constraint is met with equality there: weakly active), or the quotient of one row, or
+	// one bound; above the minimiser it is a lower end (row with a > 0, lb), below it an upper end.  Lowest row first.
+	ASIF_HD static int solve_1d_ws(const QpLaneData<NV, RPL> &in, int g, double (&x)[NV], int &steps, GiWorkingSet<NV> &ws)
+	{
+		static_assert(NV == 1 && G == 1, "one variable, one lane per problem");
+		const int verdict = solve_1d(in, g, x, steps);
+		const double P = 2.0 * in.Hd[0];
+		const double xu = -in.c[0] / (P > 0.0 ? P : 1.0), xs = x[0];
+		const bool up = xs > xu, down = xs < xu; // moved up onto a lower end / down onto an upper end
+		int id = -1;
+		double nrm = 0.0;
+#pragma unroll
+		for (int k = RPL - 1; k >= 0; k--) {
+			const double a = in.A[k][0];
+			const double q = in.b[k] / (a != 0.0 ? a : 1.0);
+			const bool hit = (q == xs) & ((up & (a > 0.0)) | (down & (a < 0.0)));
+			id = hit ? k : id;
+			nrm = hit ? a : nrm;
+		}
+		const bool onlb = (id < 0) & up & (in.lb[0] == xs), onub = (id < 0) & down & (in.ub[0] == xs);
+		id = onlb ? kIdLb : (onub ? kIdUb : id);
+		nrm = onlb ? 1.0 : (onub ? -1.0 : nrm);
+		ws.id[0] = id;
+		ws.nrm[0][0] = nrm;
+		ws.lam[0] = id >= 0 ? (P * xs + in.c[0]) / nrm : 0.0;
+		return verdict;
 	}
 
 	// Entry.  Non-finite data is asked for once, on the whole problem, and overrides whatever the comparisons below made
@@ -229,7 +306,11 @@ struct GiSmall {
 		return ok;
 	}
 
-	ASIF_HD static int solve_general(const QpLaneData<NV, RPL> &in, int g, int max_steps, double (&x)[NV], int &steps)
+	// WS (solve_with_pinned_ws only): the final working set is copied to *ws; every other caller compiles the code it
+	// compiled before
+	template <bool WS = false>
+	ASIF_HD static int solve_general(const QpLaneData<NV, RPL> &in, int g, int max_steps, double (&x)[NV], int &steps,
+	                                 GiWorkingSet<NV> *ws = nullptr)
 	{
 		if constexpr (NV == 1) return solve_1d(in, g, x, steps);
 		double Pinv[NV];
@@ -613,6 +694,15 @@ struct GiSmall {
 					mag += fabs(sn[s][j] * x[j]);
 				}
 				if (sid[s] >= 0 && fabs(ax - sb[s]) > kActiveTol * (1.0 + mag)) verdict = kGiUndecided;
+			}
+		}
+		if constexpr (WS) {
+#pragma unroll
+			for (int s = 0; s < NV; s++) {
+				ws->id[s] = sid[s];
+				ws->lam[s] = su[s];
+#pragma unroll
+				for (int j = 0; j < NV; j++) ws->nrm[s][j] = sn[s][j];
 			}
 		}
 		return verdict;

@@ -39,6 +39,19 @@ int launch_explicit_di(const DevOptions &o, const asif_hip_solver &S, const Filt
 int launch_explicit_p2(const DevOptions &o, const asif_hip_solver &S, const FilterArgs &a, bool assemble_only,
                        hipStream_t stream);
 
+// vector-Jacobian product of the explicit filter (k_explicit_vjp.hip): the gradient of a scalar loss with respect to
+// uDes and, on the caller-supplied path (lfh != nullptr), to Lfh, Lgh and -- through h alone -- x, given dL/duAct
+struct VjpArgs {
+	int64_t B, ld;
+	const double *x, *udes, *lfh, *lgh; // as FilterArgs
+	const double *guact;                // [nu][ld]
+	double *gudes;                      // [nu][ld]
+	double *glfh, *glgh, *gx;           // [nc][ld], [nc*nu][ld], [nx][ld]; each may be nullptr
+	int32_t *rc;
+};
+int launch_explicit_vjp_di(const DevOptions &o, const VjpArgs &a, hipStream_t stream);
+int launch_explicit_vjp_p2(const DevOptions &o, const VjpArgs &a, hipStream_t stream);
+
 // closed loop: T x (explicit filter + plant Euler step) per launch, model = DoubleIntegrator
 struct RolloutArgs {
 	int64_t B, ld;

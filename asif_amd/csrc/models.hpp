@@ -549,6 +549,7 @@ __device__ __forceinline__ double tanh_abs_accurate(double y, const TanhConsts &
 // exists so that the nu > 1 code of src/asif.cpp (:279-303 Lgh = Dh g with nu columns, :314-352 cost and clamp per
 // input) has a device path: x' = F x + G u with a non-diagonal G, five half-planes r_i - a_i . x >= 0.
 struct PlanarTwoInput {
+	static constexpr bool kIgnoresOptions = true; // no functor below reads DevOptions (k_explicit_vjp.hip)
 	static constexpr int NX = 2, NU = 2, NPSS = 5;
 	__device__ static void safetySet(const DevOptions &, const double (&x)[NX], double (&h)[NPSS], double (&Dh)[NPSS * NX])
 	{

@@ -48,12 +48,13 @@
 extern "C" {
 #endif
 
-#define ASIF_HIP_VERSION 131 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
+#define ASIF_HIP_VERSION 140 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
                               * 120: ASIF_HIP_IMPLICIT_RB (options grew at the end), asif_hip_set_learning, asif_hip_affine_replay;
                               * 130: solver.adaptive_rho_interval (struct grew at the end), polish == 2 is the dual active-set
                               *      stage of gi_small.hpp;
                               * 131: that stage eliminates variables pinned by their bounds and solves one-variable problems in
-                              *      closed form; class ASIF with one input runs on a kernel without the iterative stages */
+                              *      closed form; class ASIF with one input runs on a kernel without the iterative stages;
+                              * 140: asif_hip_filter_vjp_batch, the explicit filter's vector-Jacobian product */
 
 enum asif_hip_error {
 	ASIF_HIP_OK = 0,
@@ -296,6 +297,27 @@ int asif_hip_filter_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const doubl
 int asif_hip_filter_batch_lie(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, const double *udes,
                               const double *lfh, const double *lgh, double *uact, double *relax, int32_t *rc,
                               double *diag, void *stream);
+
+/* The explicit filter backwards (class ASIF; no counterpart in the reference, whose filter() is not differentiable code):
+ * given guact = dL/duAct of a scalar loss L, the gradient with respect to the inputs of B filter() calls, in one launch.
+ * uAct is the projection of uDes onto {Lgh u >= -Lfh - h relaxLb, lb <= u <= ub}; the kernel repeats the forward pass,
+ * takes the working set W its dual active-set stage ends with (bounds count as rows; |W| <= nu) and solves the adjoint
+ * 2 z + G_W' w = guact, G_W z = 0 in closed form:  gudes = 2 z;  for the rows k in W  glfh_k = -w_k,
+ * glgh_k = lambda_k z' - w_k uAct',  dL/dh_k = -relaxLb w_k  and  gx = Dh' dL/dh;  zero for every other row.  A constraint
+ * met with equality but outside W does not count (one-sided derivative).
+ *   lfh, lgh  both given (the rows of the _lie entry above, same layout) or both NULL (the model's own Lie derivatives).
+ *   guact[nu][ldx] in;  gudes[nu][ldx] out;  glfh[nc][ldx], glgh[(nc*nu)][ldx], gx[nx][ldx] out, each may be NULL.
+ *   With the model's own Lie derivatives glfh, glgh and gx must be NULL (ASIF_HIP_EINVAL otherwise): there x also moves
+ *   Lfh and Lgh, and the state gradient would need the model's second derivatives.  With caller-supplied ones gx is the
+ *   gradient through h alone -- the caller's own graph carries the part through lfh and lgh.
+ *   rc[i]: 1 gradient of a solved instance; -1 the forward QP is infeasible or its data are non-finite (filter() left
+ *   uAct untouched: dL/duAct passes to whatever uAct held before); 0 the exact stage left it undecided.  For -1 and 0
+ *   every gradient slot of the instance is written as 0.  Every gradient slot of every instance i < B is written.
+ * Explicit handles on DOUBLE_INTEGRATOR and PLANAR_TWO_INPUT with the default solver mode (polish == 2, with or without
+ * presolve; lanes_per_qp 0 or 1); anything else: ASIF_HIP_EUNSUPPORTED.  The handle's forward results do not change. */
+int asif_hip_filter_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, const double *udes,
+                              const double *lfh, const double *lgh, const double *guact, double *gudes, double *glfh,
+                              double *glgh, double *gx, int32_t *rc, void *stream);
 
 /* Closed loop, T control steps per launch -- the caller's side of filter(), examples/DoubleIntegrator.cpp:81-116:
  * per step  rc = filter(x, uDes, uAct, relax)  (cold start, same arithmetic as asif_hip_filter_batch), then the
