@@ -235,15 +235,18 @@ __global__ __launch_bounds__(256) void realizable_filter_kernel(RzDev z, asif_hi
 				const double hiH = fmax(hmin[0], h);     // its margin
 				hidx[0] = c1 ? fi : hidx[0];
 				hmin[0] = fmin(hmin[0], h);
-				const bool c2 = hiH < hmin[1];
+				// a facet pushed out of slot 0 goes before the one in slot 1 even at an equal margin: the slots are
+				// ordered by (h, index), so its index is the lower one
+				const bool c2 = c1 | (hiH < hmin[1]);
 				hidx[1] = c2 ? hiI : hidx[1];
 				hmin[1] = fmin(hmin[1], hiH);
 			} else {
 				double hv = h;
 				int hi_ = fi;
+				bool lt = false;
 #pragma unroll
-				for (int q = 0; q < KB; q++) { // sorted insert
-					const bool lt = hv < hmin[q];
+				for (int q = 0; q < KB; q++) { // sorted insert; once placed, the rest shifts down (lower index on ties)
+					lt = lt | (hv < hmin[q]);
 					const double tv = hmin[q];
 					const int ti = hidx[q];
 					hmin[q] = lt ? hv : tv;

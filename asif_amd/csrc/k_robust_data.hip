@@ -78,9 +78,12 @@ __device__ __forceinline__ void robust_data_rows(const RbDev &z, double x0, doub
 		const double a0 = z.hp[2 * i], a1 = z.hp[2 * i + 1];
 		double hv = 1. - a0 * x0 - a1 * x1; // examples/DoubleIntegrator_Robust.cpp:45
 		int hi_ = i;
+		bool lt = false;
+		// sorted insert, strict < (indexes arrive in increasing order); once the row is placed the rest shifts down, a
+		// row pushed past one of equal margin included: the list is ordered by (h, index) and its index is the lower
 #pragma unroll
-		for (int q = 0; q < kRbMaxRows; q++) { // sorted insert, strict < (indexes arrive in increasing order)
-			const bool lt = hv < lh[q];
+		for (int q = 0; q < kRbMaxRows; q++) {
+			lt = lt | (hv < lh[q]);
 			const double tv = lh[q];
 			const int ti = li[q];
 			lh[q] = lt ? hv : tv;
