@@ -49,7 +49,7 @@ EXPORTS = [
     "asif_hip_partition", "asif_hip_create_multi", "asif_hip_multi_destroy", "asif_hip_multi_size",
     "asif_hip_multi_handle", "asif_hip_multi_update_options", "asif_hip_filter_batch_host_multi",
     "asif_hip_filter_batch_lie", "asif_hip_filter_vjp_batch",
-    "asif_hip_math_probe", "asif_hip_qp_solve_batch_warm",
+    "asif_hip_math_probe", "asif_hip_qp_solve_batch_warm", "asif_hip_qp_vjp_batch",
 ]
 
 MODEL_DOUBLE_INTEGRATOR_SAMPLED = 4
@@ -167,6 +167,7 @@ def load():
         lib.asif_hip_rollout_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.asif_hip_set_learning.argtypes = [vp, C.POINTER(LearningData)]
         lib.asif_hip_filter_vjp_batch.argtypes = [vp, i64, i64] + [vp] * 11
+        lib.asif_hip_qp_vjp_batch.argtypes = [C.c_int, i64, i64, C.c_int32, C.c_int32] + [vp] * 17
         _lib = lib
     return _lib
 
@@ -431,6 +432,23 @@ def qp_solve_batch(Hd, c, A, b, lb, ub, sol, status, iters=None, be=None, solver
     check(load().asif_hip_qp_solve_batch(device, C.byref(s), B, c.stride(0), nv, nc, _ptr(Hd), _ptr(c), _ptr(A),
                                          _ptr(b), _ptr(lb), _ptr(ub), bep, _ptr(sol), _ptr(status), _ptr(iters),
                                          _stream()))
+
+
+def qp_vjp_batch(Hd, c, A, b, lb, ub, gsol, rc, gHd=None, gc=None, gA=None, gb=None, glb=None, gub=None, sol=None,
+                 be=None, device=0):
+    """asif_hip_qp_vjp_batch: the in-register QP solve backwards (nv 2 or 3, nc <= 48, diagonal cost).  Inputs as
+    qp_solve_batch plus gsol [nv,B] = dL/dx*; rc int32[B] out (1 solved, -1 infeasible / non-finite, 0 undecided:
+    gradients 0); gHd, gc, glb, gub [nv,B], gA [nc*nv,B], gb [nc,B], sol [nv,B] out, each optional.  Every tensor
+    shares c's leading dimension."""
+    nv, B = c.shape
+    nc = b.shape[0]
+    bep = None
+    if be is not None:
+        arr = (C.c_uint8 * nc)(*[int(v) for v in be])
+        bep = C.cast(arr, C.c_void_p)
+    check(load().asif_hip_qp_vjp_batch(device, B, c.stride(0), nv, nc, _ptr(Hd), _ptr(c), _ptr(A), _ptr(b), _ptr(lb),
+                                       _ptr(ub), bep, _ptr(gsol), _ptr(gHd), _ptr(gc), _ptr(gA), _ptr(gb), _ptr(glb),
+                                       _ptr(gub), _ptr(sol), _ptr(rc), _stream()))
 
 
 def qp_solve_batch_warm(Hd, H, c, A, b, lb, ub, sol, status, warm_x, warm_y, warm_in, iters=None, be=None,

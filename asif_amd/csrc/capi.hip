@@ -1123,6 +1123,28 @@ extern "C" int asif_hip_qp_solve_batch_dense(int device, const asif_hip_solver *
 	return qp_solve_common(device, solver, B, ld, nv, nc, nullptr, H, c, A, b, lb, ub, be, sol, status, iters, stream);
 }
 
+extern "C" int asif_hip_qp_vjp_batch(int device, int64_t B, int64_t ld, int32_t nv, int32_t nc, const double *Hd,
+                                     const double *c, const double *A, const double *b, const double *lb,
+                                     const double *ub, const uint8_t *be, const double *gsol, double *gHd, double *gc,
+                                     double *gA, double *gb, double *glb, double *gub, double *sol, int32_t *rc,
+                                     void *stream)
+{
+	if (B < 0 || ld < B || nv < 1 || nc < 0) return ASIF_HIP_EINVAL;
+	if (nv < 2 || nv > 3 || nc < 1 || nc > 48) return ASIF_HIP_EUNSUPPORTED; // the in-register shapes
+	if (B == 0) return ASIF_HIP_OK;
+	if (!Hd || !c || !A || !b || !lb || !ub || !gsol || !rc) return ASIF_HIP_EINVAL;
+	int r = check_device(device);
+	if (r) return r;
+	hipError_t e = hipSetDevice(device);
+	if (e != hipSuccess) return (int)e;
+	uint64_t mask = 0;
+	if (be)
+		for (int i = 0; i < nc; i++)
+			if (be[i]) mask |= 1ull << i;
+	const QpVjpArgs a = {B, ld, nv, nc, Hd, c, A, b, lb, ub, mask, gsol, gHd, gc, gA, gb, glb, gub, sol, rc};
+	return launch_qp_vjp(a, (hipStream_t)stream);
+}
+
 // Host buffers, SoA with leading dimension ldh (>= B): component k of instance i at base[k * ldh + i].  Strided
 // component copies go as one 2-D copy per array; the device side is dense (ld = B).
 static int filter_host_strided(asif_hip_ctx *ctx, int64_t B, int64_t ldh, const double *x, const double *udes,

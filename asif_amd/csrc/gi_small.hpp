@@ -306,8 +306,8 @@ struct GiSmall {
 		return ok;
 	}
 
-	// WS (solve_with_pinned_ws only): the final working set is copied to *ws; every other caller compiles the code it
-	// compiled before
+	// WS (solve_with_pinned_ws, and qp_vjp_solve of qp_vjp_small.hpp at NV = 2, 3 and G >= 1): the final working set is
+	// copied to *ws; every other caller compiles the code it compiled before
 	template <bool WS = false>
 	ASIF_HD static int solve_general(const QpLaneData<NV, RPL> &in, int g, int max_steps, double (&x)[NV], int &steps,
 	                                 GiWorkingSet<NV> *ws = nullptr)

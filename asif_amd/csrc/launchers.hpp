@@ -164,6 +164,21 @@ struct QpArgs {
 // pre-assembled QPs; returns ASIF_HIP_EUNSUPPORTED for shapes without a compiled kernel
 int launch_qp_small(const asif_hip_solver &S, const QpArgs &a, hipStream_t stream);
 
+// vector-Jacobian product of the in-register QP solve (k_qp_vjp.hip): inputs as QpArgs, gsol = dL/dx* [nv][ld]; every
+// output except rc may be nullptr
+struct QpVjpArgs {
+	int64_t B, ld;
+	int nv, nc;
+	const double *Hd, *c, *A, *b, *lb, *ub;
+	uint64_t be_mask;
+	const double *gsol;
+	double *gHd, *gc, *gA, *gb, *glb, *gub; // shaped like Hd, c, A, b, lb, ub
+	double *sol;                            // [nv][ld]: the optimum the kernel recomputed
+	int32_t *rc;
+};
+// ASIF_HIP_EUNSUPPORTED outside nv = 2, 3 and 1 <= nc <= 48
+int launch_qp_vjp(const QpVjpArgs &a, hipStream_t stream);
+
 // asif_hip_solver::scaling_iters: 0 = the path's default number of Ruiz passes, negative = no scaling;
 // check_interval: 0 = the path's default
 inline asif_hip_solver resolve_scaling(const asif_hip_solver &S, int path_default, int check_default = 2)

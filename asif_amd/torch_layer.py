@@ -1,10 +1,15 @@
-"""The explicit safety filter (class ASIF) as a differentiable torch layer.
+"""Differentiable torch layers on the library's kernels.
 
-Forward: asif_hip_filter_batch / asif_hip_filter_batch_lie.  Backward: one asif_hip_filter_vjp_batch launch
-(asif_amd/csrc/k_explicit_vjp.hip).  Both run on torch's current stream; nothing here computes on the CPU and
-nothing falls back to torch operators.
+The explicit safety filter (class ASIF).  Forward: asif_hip_filter_batch / asif_hip_filter_batch_lie.  Backward: one
+asif_hip_filter_vjp_batch launch (asif_amd/csrc/k_explicit_vjp.hip).
+The batched solve of small pre-assembled QPs.  Forward: asif_hip_qp_solve_batch.  Backward: one asif_hip_qp_vjp_batch
+launch (asif_amd/csrc/k_qp_vjp.hip).
+All of it runs on torch's current stream; nothing here computes on the CPU, and no solve or adjoint falls back to torch
+operators.  The torch operators that remain are bookkeeping around the launches: an instance whose forward pass failed
+has its incoming gradient routed (ExplicitFilterFn: to uact_prev) or zeroed (QPSolveFn) by one elementwise select.
 
-Tensors are FP64 CUDA tensors, structure-of-arrays: x [nx,B], udes [nu,B], lfh [nc,B], lgh [nc*nu,B].
+Tensors are FP64 CUDA tensors, structure-of-arrays: x [nx,B], udes [nu,B], lfh [nc,B], lgh [nc*nu,B]; for the QP
+Hd, c, lb, ub [nv,B], A [nc*nv,B] (entry (r, j) of the row matrix at component r + j*nc), b [nc,B].
 """
 import torch
 
@@ -81,3 +86,65 @@ class ExplicitSafetyLayer(torch.nn.Module):
 
     def forward(self, x, udes, lfh=None, lgh=None, uact_prev=None):
         return ExplicitFilterFn.apply(self.filter, x, udes, lfh, lgh, uact_prev)
+
+
+class QPSolveFn(torch.autograd.Function):
+    """sol, status = QPSolveFn.apply(Hd, c, A, b, lb, ub, be)
+
+    min x'diag(Hd)x + c'x  s.t.  A x >= b (== b for the rows flagged in be), lb <= x <= ub,  one problem per column.
+    be: a sequence of nc flags shared by the batch, or None.  nv is 2 or 3 and nc at most 48 (the shapes whose solve and
+    adjoint run in registers); anything else raises.  sol [nv,B] is differentiable with respect to all six tensors;
+    status int32[B] (1 = solved) is not.  An instance whose status is not 1, or that the backward pass's own solve does
+    not decide, gets zero gradients.  Backward is one elementwise select on gsol (the status mask) and one
+    asif_hip_qp_vjp_batch launch."""
+
+    @staticmethod
+    def forward(ctx, Hd, c, A, b, lb, ub, be):
+        if c.dim() != 2 or b.dim() != 2:
+            raise ValueError(f"c and b: expected [nv, B] and [nc, B], got {tuple(c.shape)} and {tuple(b.shape)}")
+        nv, B = c.shape
+        nc = b.shape[0]
+        if nv not in (2, 3) or not 1 <= nc <= 48:
+            raise ValueError(f"no backward pass for a {nv} x {nc} QP: nv must be 2 or 3 and 1 <= nc <= 48")
+        if be is not None and len(be) != nc:
+            raise ValueError(f"be: expected {nc} flags, got {len(be)}")
+        Hd, c, lb, ub = (_soa(t, nv, B, n) for t, n in ((Hd, "Hd"), (c, "c"), (lb, "lb"), (ub, "ub")))
+        A, b = _soa(A, nc * nv, B, "A"), _soa(b, nc, B, "b")
+        sol = torch.zeros((nv, B), dtype=torch.float64, device=c.device)
+        status = torch.zeros(B, dtype=torch.int32, device=c.device)
+        if B > 0:
+            capi.qp_solve_batch(Hd, c, A, b, lb, ub, sol, status, be=be, device=c.device.index or 0)
+        ctx.be = None if be is None else tuple(int(v) for v in be)
+        ctx.save_for_backward(Hd, c, A, b, lb, ub, status)
+        ctx.mark_non_differentiable(status)
+        return sol, status
+
+    @staticmethod
+    def backward(ctx, gsol, _gstatus):
+        Hd, c, A, b, lb, ub, status = ctx.saved_tensors
+        # Deliberately one elementwise launch in front of the kernel's.  The kernel zeroes the gradients of an instance
+        # its OWN solve does not decide; the contract here is about the status the caller saw.  The two agree whenever
+        # the forward pass decided in its exact stage, but that pass has other stages (a cost without curvature is
+        # solved by its iterations and left undecided here; the reverse, a forward failure next to rc 1, is not ruled
+        # out by construction).  Where status != 1, sol carries no value and nothing may flow back: the adjoint is
+        # linear in gsol, so a zeroed column yields zero gradients, and a column with status 1 passes through bit for bit.
+        gsol = torch.where(status == 1, gsol, torch.zeros_like(gsol)).contiguous()
+        grads = [torch.empty_like(t) if need else None
+                 for t, need in zip((Hd, c, A, b, lb, ub), ctx.needs_input_grad[:6])]
+        if c.shape[1] > 0 and any(g is not None for g in grads):
+            gHd, gc, gA, gb, glb, gub = grads
+            capi.qp_vjp_batch(Hd, c, A, b, lb, ub, gsol, torch.empty_like(status), gHd=gHd, gc=gc, gA=gA, gb=gb, glb=glb,
+                              gub=gub, be=ctx.be, device=c.device.index or 0)
+        return (*grads, None)
+
+
+class QPLayer(torch.nn.Module):
+    """A batched small QP in the middle of a model: sol, status = layer(Hd, c, A, b, lb, ub).  Holds the equality
+    flags `be` of the rows (None: all inequalities), which belong to the problem's structure, not to its data."""
+
+    def __init__(self, be=None):
+        super().__init__()
+        self.be = None if be is None else tuple(int(v) for v in be)
+
+    def forward(self, Hd, c, A, b, lb, ub):
+        return QPSolveFn.apply(Hd, c, A, b, lb, ub, self.be)

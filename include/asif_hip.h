@@ -48,13 +48,14 @@
 extern "C" {
 #endif
 
-#define ASIF_HIP_VERSION 140 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
+#define ASIF_HIP_VERSION 150 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
                               * 120: ASIF_HIP_IMPLICIT_RB (options grew at the end), asif_hip_set_learning, asif_hip_affine_replay;
                               * 130: solver.adaptive_rho_interval (struct grew at the end), polish == 2 is the dual active-set
                               *      stage of gi_small.hpp;
                               * 131: that stage eliminates variables pinned by their bounds and solves one-variable problems in
                               *      closed form; class ASIF with one input runs on a kernel without the iterative stages;
-                              * 140: asif_hip_filter_vjp_batch, the explicit filter's vector-Jacobian product */
+                              * 140: asif_hip_filter_vjp_batch, the explicit filter's vector-Jacobian product;
+                              * 150: asif_hip_qp_vjp_batch, the vector-Jacobian product of the in-register QP solve */
 
 enum asif_hip_error {
 	ASIF_HIP_OK = 0,
@@ -404,6 +405,34 @@ int asif_hip_qp_solve_batch_warm(int device, const asif_hip_solver *solver, int6
                                  const double *b, const double *lb, const double *ub, const uint8_t *be, double *sol,
                                  int32_t *status, int32_t *iters, double *warm_x, double *warm_y, int32_t warm_in,
                                  void *stream);
+
+/* asif_hip_qp_solve_batch backwards, for the shapes that run in registers: given gsol = dL/dx* of a scalar loss L, the
+ * gradient with respect to every input of B solves, in one launch.  Inputs and layout are those of
+ * asif_hip_qp_solve_batch (SoA, A(r, c) at component r + c*nc, be a HOST array or NULL).  The problem is
+ *     min x'Hx + c'x   s.t.  A x >= b (== b where be),  lb <= x <= ub,   H = diag(Hd).
+ * The kernel repeats the solve by the dual active-set method (solver.polish == 2, the default mode's exact stage) and
+ * takes the working set W it ends with: a general row k has normal a_k and right side b_k, a lower bound normal +e_j
+ * and right side lb_j, an upper bound normal -e_j and right side -ub_j; |W| <= nv; lambda its multipliers, N its
+ * normals.  With D = 2H it solves  D z + N' w = gsol,  N z = 0  in closed form (|W| = nv: z = 0 and N' w = gsol is a
+ * square system) and writes
+ *     gc = -z,   gHd_j = -2 x*_j z_j,
+ *     k in W:  gb_k = w_k,  gA_k = lambda_k z' - w_k x*',   lower bound:  glb_j = w,   upper bound:  gub_j = -w,
+ * and zero for every row and bound outside W.  A variable pinned by lb_j == ub_j sits in W as ONE equality, the one the
+ * method pre-loads in the place of the lower bound: its w is reported on glb_j, and gub_j = 0.  A constraint met with
+ * equality but outside W (multiplier zero) does not count: the one-sided derivative of the side the method ended on,
+ * as in asif_hip_filter_vjp_batch.
+ *   gsol[nv][ld] in.  gHd, gc, glb, gub [nv][ld], gA [(nc*nv)][ld], gb [nc][ld], sol [nv][ld] out; each may be NULL.
+ *   rc[B] out: 1 solved; -1 the problem is infeasible or its data are non-finite; 0 the exact stage left it undecided
+ *   (for example some Hd_j <= 0).  For -1 and 0 every gradient slot of the instance is written as 0.  Every slot of every
+ *   instance i < B of every non-NULL output is written.  sol receives the optimum the kernel recomputed; it has no
+ *   meaning where rc != 1.  What an instance receives does not depend on the other instances of the batch.
+ * Shapes: nv = 2 or 3, 1 <= nc <= 48, diagonal cost; anything else -- nv = 1, nv > 3, more rows; a full cost matrix has
+ * no argument here -- returns ASIF_HIP_EUNSUPPORTED: the adjoint of the wave-level kernels (qp_inv.hpp / qp_lds.hpp) is a
+ * later piece of work.  Bad pointers or sizes: ASIF_HIP_EINVAL.  B == 0 is a no-op returning 0. */
+int asif_hip_qp_vjp_batch(int device, int64_t B, int64_t ld, int32_t nv, int32_t nc, const double *Hd, const double *c,
+                          const double *A, const double *b, const double *lb, const double *ub, const uint8_t *be,
+                          const double *gsol, double *gHd, double *gc, double *gA, double *gb, double *glb, double *gub,
+                          double *sol, int32_t *rc, void *stream);
 
 /* Host-buffer convenience (pinned or pageable host memory, blocking): H2D, filter, D2H.  AoS->SoA is the
  * caller's business: same [component][ld] layout.  Used by the C++ class mirror for single agents. */
