@@ -722,10 +722,17 @@ static int assemble_tb(const or_model *m, const or_options *o, const double *x, 
 	double cosTilde[1] = {0}, fClBS[OR_MAX_NX], DfClBS[OR_MAX_NX * OR_MAX_NX];
 	double den1 = 0, den2 = 0, den = 0, ortho = 0;
 	const double *btX = 0;
+	/* not the reference's: how close the scan came to deciding otherwise (diag[3], diag[4]) */
+	double hBSAtHit = 0.0, hBSMaxMiss;
+	m->backup(o, x, hBS, DhBS, DDhBS);
+	hBSMaxMiss = hBS[0];
+	hBS[0] = 0;
 	for (int i = 1; i < T.npBT; i++) {
 		if (hBSnm1 < 0.0) {
 			m->backup(o, T.z + (size_t)i * T.nz, hBS, DhBS, DDhBS);
+			if (hBS[0] < 0.0 && hBS[0] > hBSMaxMiss) hBSMaxMiss = hBS[0];
 			if (hBS[0] >= 0.0) {
+				hBSAtHit = hBS[0];
 				idxHit = i;
 				BSHit = 1;
 				btX = T.z + (size_t)i * T.nz;
@@ -743,6 +750,8 @@ static int assemble_tb(const or_model *m, const or_options *o, const double *x, 
 	if (!BSHit) {
 		if (diag) {
 			diag[1] = 0;
+			diag[3] = 0;
+			diag[4] = hBSMaxMiss;
 		}
 		traj_free(&T);
 		return -1;
@@ -816,6 +825,8 @@ static int assemble_tb(const or_model *m, const or_options *o, const double *x, 
 		diag[0] = TTS;
 		diag[1] = ortho;
 		diag[2] = (double)idxHit;
+		diag[3] = hBSAtHit;
+		diag[4] = hBSMaxMiss;
 	}
 	traj_free(&T);
 	return 1;
@@ -905,6 +916,7 @@ int or_assemble(int model, int variant, const or_options *o, const double *x, do
 		m->backup(o, x, hb, Dhb, DDhb);
 		if (hb[0] >= 0) {
 			assemble_tb_trivial(o, d.nc, d.nv, A, b, diag);
+			if (diag) diag[3] = hb[0];
 			return 2;
 		}
 		int r = assemble_tb(m, o, x, A, b, diag);
@@ -914,6 +926,43 @@ int or_assemble(int model, int variant, const or_options *o, const double *x, do
 		return assemble_robust(m, o, x, A, b);
 	}
 	return -100;
+}
+
+/* The model callbacks at given states (or_oracle.h): what tests that build states by construction, or check a plant
+ * step, need of a model without going through an assembly. */
+int64_t or_model_eval_batch(int model, const or_options *o, int64_t B, const double *x, double *f, double *g,
+                            double *fCl, double *hBS, double *DhBS, double *fDiff)
+{
+	const or_model *m = or_model_get(model);
+	if (!m || B < 0) return -1;
+	if (((f || g || fDiff) && !m->dynamics) || (fCl && !(m->dynamics && m->gradients && m->controller)) ||
+	    ((hBS || DhBS) && !m->backup))
+		return -1;
+	const int nx = m->nx, nu = m->nu, nb = m->npBS;
+	for (int64_t i = 0; i < B; i++) {
+		const double *xi = x + i * nx;
+		double fi[OR_MAX_NX], gi[OR_MAX_NX * OR_MAX_NU], fc[OR_MAX_NX], DfCL[OR_MAX_NX * OR_MAX_NX];
+		double hb[OR_MAX_NPSS], Dhb[OR_MAX_NPSS * OR_MAX_NX], DDhb[OR_MAX_NX * OR_MAX_NX];
+		if (f || g) {
+			m->dynamics(o, xi, fi, gi);
+			if (f) memcpy(f + i * nx, fi, nx * sizeof(double));
+			if (g) memcpy(g + i * nx * nu, gi, nx * nu * sizeof(double));
+		}
+		if (fCl) {
+			backup_cl(m, o, xi, fc, DfCL, 0, 0.0);
+			memcpy(fCl + i * nx, fc, nx * sizeof(double));
+		}
+		if (fDiff) {
+			(m->dynamics_diff ? m->dynamics_diff : m->dynamics)(o, xi, fi, gi);
+			memcpy(fDiff + i * nx, fi, nx * sizeof(double));
+		}
+		if (hBS || DhBS) {
+			m->backup(o, xi, hb, Dhb, DDhb);
+			if (hBS) memcpy(hBS + i * nb, hb, nb * sizeof(double));
+			if (DhBS) memcpy(DhBS + i * nb * nx, Dhb, nb * nx * sizeof(double));
+		}
+	}
+	return B;
 }
 
 /* Cost / bounds / equality flags each variant hands to QPWrapperAbstract::initialize + updateCost:

@@ -23,6 +23,9 @@ typedef struct {
 	 * only h is consumed by the reference (src/asif_implicit_robust.cpp:645-647), Dh_int feeds dead code */
 	void (*safety_af)(const void *ud, or_af_ctx *cx, const or_af *x, or_af *h);
 	int npBTSS; /* critical samples kept by the implicit variant (constructor argument of the example) */
+	/* the dynamics `gradients` is the Jacobian of, where that is not `dynamics` (the segway: the example zeroes the
+	 * friction in f and ships the Jacobian with it); NULL otherwise.  No filter calls it. */
+	void (*dynamics_diff)(const void *ud, const double *x, double *f, double *g);
 } or_model;
 
 const or_model *or_model_get(int id);

@@ -202,11 +202,12 @@ static void sg_ctrl(const void *ud, const double *x, double *u, double *Du)
 	for (int i = 0; i < 4; i++) Du[i] = sg_K[i];
 }
 
-static void sg_dynamics(const void *ud, const double *X, double *f, double *g)
+/* kf is the reference's literal 0.0 in front of the friction term (:78); 1.0 gives the f its Jacobian was generated
+ * from (sg_dynamics_diff below) */
+static inline void sg_dynamics_k(const double *X, double *f, double *g, const double kf)
 {
-	(void)ud;
 	/* :70-111 */
-	const double Fric = 0.0 * 2.595498 * tanh(X[1] / 0.001);
+	const double Fric = kf * 2.595498 * tanh(X[1] / 0.001);
 	const double w2 = X[3] * X[3];
 	const double s1 = sin(X[2]);
 	const double s2 = sin(2.0 * X[2]);
@@ -238,6 +239,20 @@ static void sg_dynamics(const void *ud, const double *X, double *f, double *g)
 	               -0.29573215449441 * s2));
 	g[2] = 0.0;
 	g[3] = -5.65378660671284 * ((2.0043013906215941 + gc) + gs) * iden;
+}
+
+static void sg_dynamics(const void *ud, const double *X, double *f, double *g)
+{
+	(void)ud;
+	sg_dynamics_k(X, f, g, 0.0);
+}
+
+/* NOT called by any filter: the dynamics sg_grad below is the Jacobian of (friction term live), for the tests that
+ * difference a flow to check the sensitivity (or_model_eval_batch: fDiff) */
+static void sg_dynamics_diff(const void *ud, const double *X, double *f, double *g)
+{
+	(void)ud;
+	sg_dynamics_k(X, f, g, 1.0);
 }
 
 static void sg_grad(const void *ud, const double *x, double *Df, double *Dg)
@@ -455,14 +470,14 @@ static void p2_dynamics(const void *ud, const double *x, double *f, double *g)
 }
 
 static const or_model MODELS[8] = {
-    {2, 1, 4, 0, di_safety, 0, di_dynamics, 0, 0, 0, 0, 0},
-    {2, 1, 4, 1, ip_safety, ip_backup, ip_dynamics, ip_grad, ip_ctrl, 0, ip_safety_af, 10}, /* examples/InvertedPendulum_Implicit.cpp:17 */
-    {4, 1, 4, 1, sg_safety, sg_backup, sg_dynamics, sg_grad, sg_ctrl, 0, 0, 4},
-    {2, 1, 0, 0, ipr_safety, 0, 0, 0, 0, ipr_dynamics_af, 0, 0},
-    {2, 1, 4, 1, ipt_safety, ipt_backup, ip_dynamics, ip_grad, ipt_ctrl, 0, 0, 4}, /* dynamics :67-74,87-94 = the pendulum's */
-    {2, 1, 4, 1, dii_safety, dii_backup, di_dynamics, dii_grad, dii_ctrl, 0, dii_safety_af, 4}, /* dynamics :57-63 = A x, B; npBTSS :17 */
-    {2, 2, 5, 0, p2_safety, 0, p2_dynamics, 0, 0, 0, 0, 0},
-    {2, 1, 4, 1, dii_safety, dit_backup, di_dynamics, dii_grad, dii_ctrl, 0, 0, 4}, /* box :33-39, A x, B :59-65, K :67-74 as the implicit example; npBTSS :16 */
+    {2, 1, 4, 0, di_safety, 0, di_dynamics, 0, 0, 0, 0, 0, 0},
+    {2, 1, 4, 1, ip_safety, ip_backup, ip_dynamics, ip_grad, ip_ctrl, 0, ip_safety_af, 10, 0}, /* examples/InvertedPendulum_Implicit.cpp:17 */
+    {4, 1, 4, 1, sg_safety, sg_backup, sg_dynamics, sg_grad, sg_ctrl, 0, 0, 4, sg_dynamics_diff},
+    {2, 1, 0, 0, ipr_safety, 0, 0, 0, 0, ipr_dynamics_af, 0, 0, 0},
+    {2, 1, 4, 1, ipt_safety, ipt_backup, ip_dynamics, ip_grad, ipt_ctrl, 0, 0, 4, 0}, /* dynamics :67-74,87-94 = the pendulum's */
+    {2, 1, 4, 1, dii_safety, dii_backup, di_dynamics, dii_grad, dii_ctrl, 0, dii_safety_af, 4, 0}, /* dynamics :57-63 = A x, B; npBTSS :17 */
+    {2, 2, 5, 0, p2_safety, 0, p2_dynamics, 0, 0, 0, 0, 0, 0},
+    {2, 1, 4, 1, dii_safety, dit_backup, di_dynamics, dii_grad, dii_ctrl, 0, 0, 4, 0}, /* box :33-39, A x, B :59-65, K :67-74 as the implicit example; npBTSS :16 */
 };
 
 const or_model *or_model_get(int id)

@@ -182,7 +182,9 @@ int or_qp_admm(const or_qp *qp, const or_admm_settings *s, double *x, or_admm_in
 
 /* ------------------------------------------------------------ assembly */
 /* updateConstraints() of the given variant: fills A (nc x nv col-major), b[nc].
- * diag (optional, >= 8 doubles): [0]=TTS_, [1]=BTorthoBS_, [2]=idxHit, [3..]=reserved.
+ * diag (optional, >= 8 doubles): [0]=TTS_, [1]=BTorthoBS_, [2]=idxHit; TB only, and not the reference's: [3]=the
+ * backup-set function at the hit sample (code 2: at x), [4]=its value closest to zero among the samples scanned
+ * before the hit (code -3: among all) -- how far the scan was from deciding otherwise; [5..]=reserved.
  * Returns the variant's own code: 1 ok; TB: 2 = inside backup set (trivial rows),
  * -3 = backup set never reached (A,b untouched). */
 int or_assemble(int model, int variant, const or_options *o, const double *x, double *A, double *b, double *diag);
@@ -288,6 +290,15 @@ int64_t or_rb_filter_batch(const or_rb *z, int solver, const or_admm_settings *s
                            const double *uDes, double *uAct, double *relax, int32_t *rc);
 int64_t or_rb_assemble_batch(const or_rb *z, int64_t B, const double *x, double *A, double *b, int32_t *code,
                              int32_t *sel);
+
+/* The model's own functions at B states x[B][nx], as the filter classes call them: f[B][nx], g[B][nx*nu] the open-loop
+ * dynamics; fCl[B][nx] the closed-loop backup flow f + g sat(u_backup) (src/asif_implicit.cpp:751-815, saturation by
+ * o->lb / ub / satSharpness); hBS[B][npBS], DhBS[B][npBS*nx] the backup set and its gradient; fDiff[B][nx] the f that
+ * the model's Jacobian callback differentiates -- f itself except on the segway, whose example zeroes the friction
+ * term in f and ships the Jacobian generated with it (no filter evaluates fDiff).  Any output may be NULL.
+ * Returns B, or -1 for an unknown model or one without a function that was asked for. */
+int64_t or_model_eval_batch(int model, const or_options *o, int64_t B, const double *x, double *f, double *g,
+                            double *fCl, double *hBS, double *DhBS, double *fDiff);
 
 /* SURVEY 8(d) RNG: splitmix64(seed*2^32 + k) -> r=(z>>11)*2^-53, k = i*16+j */
 double or_rng_uniform(uint64_t seed, uint64_t i, uint64_t j);

@@ -55,6 +55,26 @@ def run_assemble(cfg, B, first=0, options=None, x=None, learning=None, model=Non
     return out
 
 
+def child_digests(body, env, timeout=600):
+    """sha256 of rows, diagnostics and filter outputs computed in a process of its own -- for the developer switches
+    the library reads once per process.  `body`: Python source that leaves r = run_assemble(...) and
+    f = run_filter(..., uact_init=7.0, relax_init=-7.0); gpu_util, capi and numpy (np) are imported for it."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys, json, hashlib; sys.path.insert(0, %r); sys.path.insert(0, %r + '/tests'); import gpu_util\n"
+            "import numpy as np\nfrom asif_amd import capi\n" % (root, root) + body.rstrip("\n") + "\n"
+            "print(json.dumps({k: hashlib.sha256(v.tobytes()).hexdigest() for k, v in "
+            "(('A', r['A']), ('b', r['b']), ('code', r['code']), ('diag', r['diag']), ('uact', f['uact']), "
+            "('relax', f['relax']), ('rc', f['rc']))}))\n")
+    o = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True,
+                       timeout=timeout)
+    assert o.returncode == 0, o.stderr[-1500:]
+    return json.loads(o.stdout.strip().split("\n")[-1])
+
+
 def oracle_filter(oracle, cfg, x, udes, uact_init=0.0, relax_init=0.0, solver=0, settings=None):
     """Oracle answer for SoA inputs; untouched slots keep the init value like the device path."""
     model, variant = oracle.CONFIGS[cfg]

@@ -191,6 +191,23 @@ def assemble_batch(model, variant, o, x):
     return A, b, code, diag
 
 
+def model_eval(model, variant, o, x):
+    """The model's own functions at the rows of x [B,nx] (or_model_eval_batch): dict of f [B,nx], g [B,nx*nu] (open
+    loop), fCl [B,nx] (closed-loop backup flow under o's saturation), hBS [B], DhBS [B,nx] (backup set), fDiff [B,nx]
+    (the f the model's Jacobian is the derivative of: f, except on the segway)."""
+    d = dims(model, variant, o)
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, d.nx)
+    B = x.shape[0]
+    out = dict(f=np.zeros((B, d.nx)), g=np.zeros((B, d.nx * d.nu)), fCl=np.zeros((B, d.nx)), hBS=np.zeros(B),
+               DhBS=np.zeros((B, d.nx)), fDiff=np.zeros((B, d.nx)))
+    assert d.npBS == 1
+    lib().or_model_eval_batch.restype = C.c_int64
+    n = lib().or_model_eval_batch(model, C.byref(o), C.c_int64(B), _p(x), _p(out["f"]), _p(out["g"]), _p(out["fCl"]),
+                                  _p(out["hBS"]), _p(out["DhBS"]), _p(out["fDiff"]))
+    assert n == B
+    return out
+
+
 def qp_static(model, variant, o, udes):
     d = dims(model, variant, o)
     Hd, c, lb, ub = (np.zeros(d.nv) for _ in range(4))

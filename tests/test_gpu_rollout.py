@@ -151,7 +151,14 @@ def test_two_stage_filters_closed_loop(hip, oracle, cfg, T, dt):
         if f is not None:
             np.testing.assert_allclose(nxt, xt + dt * (f + g * ulog[t, 0]), rtol=0, atol=1e-15)
         else:
-            assert np.abs(nxt - xt).max() < 1.0 and np.abs(nxt - xt).max() > 0.0
+            # segway: f, g from the oracle.  The device's step uses its own sin / cos (1.5 ulp) and contracted
+            # multiply-adds inside f, so not to the last bit: 4 ulp of |x| + dt (|f| + |g u|) (measured: 1.93)
+            e = oracle.model_eval(omodel, ovariant, oo, np.ascontiguousarray(xt.T))
+            f, g = e["f"].T, e["g"].T
+            size = np.abs(xt) + dt * (np.abs(f) + np.abs(g * ulog[t, 0])) + 1e-300
+            gap = np.abs(nxt - (xt + dt * (f + g * ulog[t, 0]))) / (np.finfo(np.float64).eps * size)
+            print(f"\nsegway plant step {t}: worst gap {gap.max():.3g} ulp of |x| + dt (|f| + |g u|)")
+            assert gap.max() <= 4.0 and np.abs(nxt - xt).max() > 0.0
     assert np.array_equal(nfail.cpu().numpy(), (rclog < 0).sum(axis=0))
     assert np.array_equal(uact.cpu().numpy()[0], ulog[-1, 0])
     # and it is T single filter launches with the plant step in between

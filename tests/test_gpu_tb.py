@@ -77,23 +77,8 @@ def test_two_role_pass_is_bitwise_the_fused_pass(hip):
     against the fused pass (ASIF_HIP_TB_SPLIT=0, read once per process: each side in its own process): rows, diagnostics,
     uAct, relax, rc bitwise identical on a ragged batch that mixes all three branches -- a batch above the switch-over and
     its shards below it must agree, which is what the multi-GPU path is tested on."""
-    import hashlib
-    import json
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import sys, json, hashlib; sys.path.insert(0, %r); sys.path.insert(0, %r + '/tests'); import gpu_util\n"
-            "r = gpu_util.run_assemble(4, 4099); f = gpu_util.run_filter(4, 4099, uact_init=7.0, relax_init=-7.0)\n"
-            "print(json.dumps({k: hashlib.sha256(v.tobytes()).hexdigest() for k, v in "
-            "(('A', r['A']), ('b', r['b']), ('code', r['code']), ('diag', r['diag']), ('uact', f['uact']), ('relax', f['relax']), ('rc', f['rc']))}))\n"
-            % (root, root))
-    res = []
-    for v in ("1", "0"):
-        o = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, ASIF_HIP_TB_SPLIT=v), capture_output=True,
-                           text=True, timeout=300)
-        assert o.returncode == 0, o.stderr[-1500:]
-        res.append(json.loads(o.stdout.strip().split("\n")[-1]))
+    body = "r = gpu_util.run_assemble(4, 4099); f = gpu_util.run_filter(4, 4099, uact_init=7.0, relax_init=-7.0)\n"
+    res = [gpu_util.child_digests(body, {"ASIF_HIP_TB_SPLIT": v}, timeout=300) for v in ("1", "0")]
     assert res[0] == res[1]
 
 

@@ -3,32 +3,19 @@ small launches and four from two waves per CU on (launchers.hpp: waves_per_workg
 and the trajectory kernels choose between LDS layouts and pass forms by batch size: rows, diagnostics, uAct, relax and rc
 of the same instances are the same BITS whichever was taken -- compared across processes (the switch is read once per
 process) on ragged batches, and between a batch and the prefix of a larger one that takes the other path."""
-import hashlib
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import gpu_util
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _digests(cfg, B, env, integrator=0):
-    code = ("import sys, json, hashlib; sys.path.insert(0, %r); sys.path.insert(0, %r + '/tests'); import gpu_util\n"
-            "from asif_amd import capi\n"
-            "o = capi.default_options(*capi.CONFIGS[%d][:2]); o.integrator = %d\n" % (ROOT, ROOT, cfg, integrator) +
+    body = ("o = capi.default_options(*capi.CONFIGS[%d][:2]); o.integrator = %d\n" % (cfg, integrator) +
             "r = gpu_util.run_assemble(%d, %d, options=o); f = gpu_util.run_filter(%d, %d, options=o, uact_init=7.0, relax_init=-7.0)\n"
-            "print(json.dumps({k: hashlib.sha256(v.tobytes()).hexdigest() for k, v in "
-            "(('A', r['A']), ('b', r['b']), ('code', r['code']), ('diag', r['diag']), ('uact', f['uact']), "
-            "('relax', f['relax']), ('rc', f['rc']))}))\n" % (cfg, B, cfg, B))
-    o = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
-    assert o.returncode == 0, o.stderr[-1500:]
-    return json.loads(o.stdout.strip().split("\n")[-1])
+            % (cfg, B, cfg, B))
+    return gpu_util.child_digests(body, env)
 
 
 @pytest.mark.parametrize("cfg,B", [(3, 1000), (9, 4099), (12, 4099), (8, 300), (4, 4099), (5, 4099), (10, 300), (11, 4099)])

@@ -17,6 +17,7 @@ J = Q - fCL (grad h_B Q) without the 1 / (grad h_B . fCL) of the hitting map and
     row = (1 - grad h_B . fCL) / |fCL|  *  grad h_B' DfCL J ,
 which the second test evaluates with a sensitivity Q obtained by differencing this file's own flow at the hit time."""
 import numpy as np
+import pytest
 
 LB, UB, R_SAT = -1.5, 1.5, 0.1
 
@@ -143,6 +144,107 @@ def test_ortho_row_is_the_reference_formula(oracle):
         np.testing.assert_allclose(Am[17, 0], row @ g, rtol=5e-2, atol=2e-4)
         checked += 1
     assert checked >= 8
+
+
+# ---- the segway on states that reach the backup set late (tests/synth_states.py).  The check through the CONTINUOUS
+# hitting map above does not carry over: the segway's backup set is a small ellipsoid (0.157 rad/s wide in the pitch
+# rate) that the closed loop crosses in a few Euler steps, so the sample at which forward Euler lands inside it is not
+# within O(dt) of where the continuous flow crosses (measured with RK4 + bisection: the two derivatives differ by
+# 10 % to 30 x).  Nor are the rows derivatives of the map the class integrates: the example zeroes the friction term
+# in f and ships the Jacobian generated WITH it (examples/segway_implicit_tb.cpp:78 against :113-212), so the
+# sensitivity is Q_{i+1} = Q_i + dt DfCL~(x_i) Q_i along the friction-free trajectory x_i, DfCL~ the Jacobian of the
+# closed loop with friction (measured: differencing the integrated flow itself is off by O(1) in some rows).  That
+# recursion is what is rebuilt here, with DfCL~(x_i) w taken by central differences of the flow alone (the oracle's
+# fCl - f + fDiff export): the transcribed Jacobian, the saturation's slope, the recursion over up to 315 steps and the
+# row formulas at the critical samples and at the hit are checked against something that contains none of them.
+
+def _euler_path(fcl, x0, dt, n):
+    """[n, B, nx]: the samples of forward Euler from the rows of x0, with the oracle's own two roundings per step."""
+    out = np.empty((n,) + x0.shape)
+    out[0] = x0
+    for i in range(1, n):
+        out[i] = fcl(out[i - 1]) * dt + out[i - 1]
+    return out
+
+
+def _central(fun, x, v, eps):
+    """d fun(x + s v) / ds at 0 by central differences, v scaled to unit length per row for the step."""
+    s = np.linalg.norm(v, axis=-1, keepdims=True)
+    s = np.where(s > 0, s, 1.0)
+    return (fun(x + eps * v / s) - fun(x - eps * v / s)) / (2 * eps) * s
+
+
+@pytest.mark.parametrize("name", ["fine_step", "default"])
+def test_segway_rows_on_late_hits_against_a_differenced_flow(oracle, name):
+    import synth_states as S
+    fam = S.late_hit_family(oracle, name)
+    o, npBT, dt = fam["o"], fam["npBT"], fam["o"].backTrajDt
+    ev = lambda X: oracle.model_eval(S.MODEL, S.VARIANT, o, X)
+    fcl = lambda X: ev(X)["fCl"]
+
+    def fcl_diff(X):  # the closed loop whose Jacobian the class propagates
+        e = ev(X)
+        return e["fCl"] - e["f"] + e["fDiff"]
+    hit = fam["diag"][:, 2].astype(int)
+    m = fam["code"] == 1
+    # a sample over the whole trajectory: past the first two blocks, some in the last block and on the last sample
+    late = np.where(m & (hit >= 2 * S.BLOCK) & (hit < npBT - S.BLOCK))[0]
+    idx = np.concatenate([late[:: max(1, len(late) // 16)][:16], np.where(m & (hit >= npBT - S.BLOCK))[0][:6],
+                          np.where(m & (hit == npBT - 1))[0][:2]])
+    x, k, crit = fam["x"][idx], hit[idx], fam["crit"][idx]
+    n = len(idx)
+    assert n >= 20 and np.all(crit >= 0)
+    e0 = ev(x)
+    rows = np.arange(n)
+    A = fam["A"][idx].reshape(n, 2, 18)
+    b = fam["b"][idx]
+    X = _euler_path(fcl, x, dt, npBT)
+    xk, xc = X[k, rows], X[crit.T, rows]  # hit sample [n, nx]; critical samples [4, n, nx]
+    ek = ev(xk)
+    fk, Dh = ek["fCl"], ek["DhBS"]
+    cos = (Dh * fk).sum(axis=1)
+    den1, den2 = np.linalg.norm(Dh, axis=1), np.linalg.norm(fk, axis=1)
+    den = den1 * den2
+    np.testing.assert_allclose(fam["diag"][idx, 1], cos / den, rtol=1e-12)  # BTorthoBS_ itself
+    np.testing.assert_allclose(fam["diag"][idx, 0], k * dt, rtol=1e-12)     # TTS_ (accumulated sample times)
+    np.testing.assert_allclose(A[:, 1, :16], (S.XB ** 2 - xc ** 2).transpose(1, 0, 2).reshape(n, 16), rtol=1e-12)
+    assert np.all(A[:, 1, 16:] == 0.0)
+
+    def rows_from(v, eps):
+        P = np.empty((npBT, n, 4))
+        P[0] = v
+        for i in range(1, npBT):
+            P[i] = P[i - 1] + dt * _central(fcl_diff, X[i - 1], P[i - 1], eps)
+        out = np.zeros((n, 18))
+        for j in range(4):  # safety rows: h_i = xBound_i^2 - x_i^2 at the four critical samples
+            out[:, 4 * j:4 * j + 4] = -2.0 * xc[j] * P[crit[:, j], rows]
+        Qv = P[k, rows]
+        DhQv = (Dh * Qv).sum(axis=1)
+        out[:, 16] = DhQv / cos  # time-to-safety row
+        # orthogonality row as the reference books it (module docstring), its two Jacobians differenced too
+        Jv = Qv - fk * DhQv[:, None]
+        t2 = _central(fcl_diff, xk, Jv, eps)
+        t1 = _central(lambda Y: ev(Y)["DhBS"], xk, Jv, eps)
+        Dden1, Dden2 = (Dh * t2).sum(axis=1), (t1 * fk).sum(axis=1)
+        Dden = den2 * Dden1 / den1 + den1 * Dden2 / den2
+        out[:, 17] = ((Dden1 + Dden2) * den - cos * Dden) / (den * den)
+        return out
+
+    for v, got, sign, in_b in ((e0["g"], A[:, 0, :], 1.0, False), (e0["f"], b, -1.0, True)):
+        want = sign * rows_from(v, 1e-6)
+        err = np.abs(sign * rows_from(v, 2e-6) - want)
+        if in_b:  # b carries the relaxation of the two extra rows
+            want[:, 16] -= o.relaxTTS * (o.backTrajHorizon - k * dt)
+            want[:, 17] -= o.relaxMinOrtho * (cos / den - o.backTrajMinOrtho)
+        # bound: the difference quotients' own error, read off the same computation at twice the step (truncation is a
+        # third of that for a smooth map; the saturation's bevels and tanh(1000 x1) are not smooth at that scale, hence
+        # the whole of it), plus their rounding: 1e-16 |fCl| / eps = 1e-10 per step and unit, 300 steps, and a factor 30
+        # for the cancellation in the rows -- 1e-6 of the instance's largest row entry
+        tol = err + 1e-6 * np.abs(want).max(axis=1, keepdims=True)
+        gap = np.abs(got - want)
+        print(f"\n{name} {'b' if in_b else 'A'}: worst |row - rebuilt row| = {(gap / tol).max():.3g} of its bound, "
+              f"{(gap / np.abs(want).max(axis=1, keepdims=True)).max():.3g} of the instance's largest entry")
+        assert np.all(gap <= tol), (np.argwhere(gap > tol)[:5], (gap / tol).max())
 
 
 # ---- the double integrator of examples/DoubleIntegrator_implicit_tb.cpp: a CURVED backup set (disc of radius 0.01),
