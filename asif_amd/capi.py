@@ -49,7 +49,7 @@ EXPORTS = [
     "asif_hip_partition", "asif_hip_create_multi", "asif_hip_multi_destroy", "asif_hip_multi_size",
     "asif_hip_multi_handle", "asif_hip_multi_update_options", "asif_hip_filter_batch_host_multi",
     "asif_hip_filter_batch_lie", "asif_hip_filter_vjp_batch",
-    "asif_hip_math_probe", "asif_hip_qp_solve_batch_warm", "asif_hip_qp_vjp_batch",
+    "asif_hip_math_probe", "asif_hip_qp_solve_batch_warm", "asif_hip_qp_vjp_batch", "asif_hip_rollout_vjp_batch",
 ]
 
 MODEL_DOUBLE_INTEGRATOR_SAMPLED = 4
@@ -168,6 +168,7 @@ def load():
         lib.asif_hip_set_learning.argtypes = [vp, C.POINTER(LearningData)]
         lib.asif_hip_filter_vjp_batch.argtypes = [vp, i64, i64] + [vp] * 11
         lib.asif_hip_qp_vjp_batch.argtypes = [C.c_int, i64, i64, C.c_int32, C.c_int32] + [vp] * 17
+        lib.asif_hip_rollout_vjp_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double] + [vp] * 13
         _lib = lib
     return _lib
 
@@ -267,6 +268,18 @@ class Filter:
         B = x.shape[1]
         check(self.lib.asif_hip_rollout_batch(self.handle, B, x.stride(0), T, dt, _ptr(x), _ptr(udes), _ptr(uact),
                                               _ptr(relax), _ptr(nfail), _ptr(xlog), _ptr(ulog), _ptr(rclog), _stream()))
+
+    def rollout_vjp(self, T, dt, xlog, ulog, rclog, udes, gxT, gx0, gudes, guact0, nskip, guactT=None, gxlog=None,
+                    gulog=None):
+        """The fused explicit rollout backwards (asif_hip_rollout_vjp_batch), one launch: xlog [T,nx,B], ulog [T,nu,B],
+        rclog int32 [T,B] as rollout() logged them, udes [nu,B]; gxT [nx,B] = dL/dx_T and, each optional, guactT [nu,B],
+        gxlog, gulog (shaped like the logs) in; gx0 [nx,B], gudes [nu,B], guact0 [nu,B], nskip int32[B] out.  Every
+        tensor shares gxT's leading dimension."""
+        B = gxT.shape[1]
+        check(self.lib.asif_hip_rollout_vjp_batch(self.handle, B, gxT.stride(0), T, dt, _ptr(xlog), _ptr(ulog),
+                                                  _ptr(rclog), _ptr(udes), _ptr(gxT), _ptr(guactT), _ptr(gxlog),
+                                                  _ptr(gulog), _ptr(gx0), _ptr(gudes), _ptr(guact0), _ptr(nskip),
+                                                  _stream()))
 
     def assemble(self, x, A, b, code, diag=None):
         B = x.shape[1]

@@ -1052,6 +1052,28 @@ extern "C" int asif_hip_rollout_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx,
 	return ASIF_HIP_OK;
 }
 
+extern "C" int asif_hip_rollout_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt,
+                                          const double *xlog, const double *ulog, const int32_t *rclog,
+                                          const double *udes, const double *gxT, const double *guactT,
+                                          const double *gxlog, const double *gulog, double *gx0, double *gudes,
+                                          double *guact0, int32_t *nskip, void *stream)
+{
+	if (!ctx || B < 0 || ldx < B || T < 0) return ASIF_HIP_EINVAL;
+	if (B > 0 && (!udes || !gxT || !gx0 || !gudes || !guact0 || !nskip)) return ASIF_HIP_EINVAL;
+	if (B > 0 && T > 0 && (!xlog || !ulog || !rclog)) return ASIF_HIP_EINVAL; // no step, no log to read
+	// the fused forward rollout exists for this model alone
+	if (ctx->variant != ASIF_HIP_EXPLICIT || ctx->rz || ctx->rb || ctx->model != ASIF_HIP_MODEL_DOUBLE_INTEGRATOR)
+		return ASIF_HIP_EUNSUPPORTED;
+	const asif_hip_solver &S = ctx->solver;
+	// as asif_hip_filter_vjp_batch: the sweep repeats each step's solve in the default solver mode
+	if (S.polish != 2 || (S.lanes_per_qp != 0 && S.lanes_per_qp != 1)) return ASIF_HIP_EUNSUPPORTED;
+	if (B == 0) return ASIF_HIP_OK;
+	hipError_t e = hipSetDevice(ctx->device);
+	if (e != hipSuccess) return (int)e;
+	const RolloutVjpArgs a = {B, ldx, T, dt, xlog, ulog, rclog, udes, gxT, guactT, gxlog, gulog, gx0, gudes, guact0, nskip};
+	return launch_rollout_vjp_explicit_di(ctx->dev, a, (hipStream_t)stream);
+}
+
 extern "C" int asif_hip_assemble_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, double *A,
                                        double *b, int32_t *code, double *diag, void *stream)
 {

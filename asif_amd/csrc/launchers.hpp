@@ -67,6 +67,22 @@ struct RolloutArgs {
 	int32_t *rclog;     // [T][ld], or nullptr
 };
 int launch_rollout_explicit_di(const DevOptions &o, const asif_hip_solver &S, const RolloutArgs &a, hipStream_t stream);
+// the fused explicit rollout backwards (k_rollout_vjp.hip): one sweep t = T-1 ... 0 over the forward pass's logs
+struct RolloutVjpArgs {
+	int64_t B, ld;
+	int T;
+	double dt;
+	const double *xlog, *ulog; // [T][nx][ld], [T][nu][ld] as RolloutArgs wrote them
+	const int32_t *rclog;      // [T][ld]
+	const double *udes;        // [nu][ld]
+	const double *gxT;         // [nx][ld] dL/dx_T
+	const double *guactT;      // [nu][ld] dL/duact_out, or nullptr: zero
+	const double *gxlog;       // [T][nx][ld], or nullptr
+	const double *gulog;       // [T][nu][ld], or nullptr
+	double *gx0, *gudes, *guact0; // [nx][ld], [nu][ld], [nu][ld]
+	int32_t *nskip;               // [B] steps with rclog == 1 that the kernel's own solve did not decide
+};
+int launch_rollout_vjp_explicit_di(const DevOptions &o, const RolloutVjpArgs &a, hipStream_t stream);
 // plant Euler step x += dt (f(x) + g(x) uact) between two filter calls of the two-stage filters (k_rollout.hip);
 // logs the state / input / rc of the call just made (nullptr to skip) and counts rc < 0 into nfail
 int launch_plant_step(int model, const DevOptions &o, int64_t B, int64_t ld, double dt, double *x, const double *uact,

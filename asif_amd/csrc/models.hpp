@@ -335,6 +335,25 @@ struct DoubleIntegrator {
 		g[0] = 0.0;
 		g[1] = 1.0;
 	}
+	// Second derivatives, for the adjoint of the closed loop (rollout_vjp_step.hpp; the reference has no counterpart).
+	// D2h[r + NPSS * (k + NX * m)] = d2 h_r / dx_k dx_m on the branch safetySet takes: the braking parabola alone bends
+	__device__ static void safetyHess(const DevOptions &, const double (&x)[NX], double (&D2h)[NPSS * NX * NX])
+	{
+		const bool fwd = x[1] > 0;
+#pragma unroll
+		for (int k = 0; k < NPSS * NX * NX; k++) D2h[k] = 0.0;
+		D2h[0 + NPSS * (1 + NX * 1)] = fwd ? -1.0 : 0.0;
+		D2h[1 + NPSS * (1 + NX * 1)] = fwd ? 0.0 : -1.0;
+	}
+	// Df column-major nx x nx (Df[k + m * NX] = d f_k / dx_m);  Dg[k + m * NX + j * NX * NX] = d g_{k,j} / dx_m
+	__device__ static void dynamicsJac(const DevOptions &, const double (&)[NX], double (&Df)[NX * NX],
+	                                   double (&Dg)[NX * NX * NU])
+	{
+		Df[0] = 0.0; Df[2] = 1.0;
+		Df[1] = 0.0; Df[3] = 0.0;
+#pragma unroll
+		for (int k = 0; k < NX * NX * NU; k++) Dg[k] = 0.0;
+	}
 };
 
 // ---------------------------------------------------------------------------------------------

@@ -2,6 +2,8 @@
 
 The explicit safety filter (class ASIF).  Forward: asif_hip_filter_batch / asif_hip_filter_batch_lie.  Backward: one
 asif_hip_filter_vjp_batch launch (asif_amd/csrc/k_explicit_vjp.hip).
+The fused explicit rollout, T x (filter + plant Euler step) on the double integrator.  Forward: asif_hip_rollout_batch.
+Backward: one asif_hip_rollout_vjp_batch launch (asif_amd/csrc/k_rollout_vjp.hip), state gradient included.
 The batched solve of small pre-assembled QPs.  Forward: asif_hip_qp_solve_batch.  Backward: one asif_hip_qp_vjp_batch
 launch (asif_amd/csrc/k_qp_vjp.hip).
 All of it runs on torch's current stream; nothing here computes on the CPU, and no solve or adjoint falls back to torch
@@ -86,6 +88,76 @@ class ExplicitSafetyLayer(torch.nn.Module):
 
     def forward(self, x, udes, lfh=None, lgh=None, uact_prev=None):
         return ExplicitFilterFn.apply(self.filter, x, udes, lfh, lgh, uact_prev)
+
+
+class ExplicitRolloutFn(torch.autograd.Function):
+    """xT, uactT, xlog, ulog, rclog, nfail = ExplicitRolloutFn.apply(flt, x0, udes, uact_prev, T, dt)
+
+    T closed-loop steps of class ASIF on the double integrator (flt: an explicit capi.Filter on that model) with udes
+    held: what a policy running at a lower rate than the filter sees between two of its calls.  uact_prev [nu,B] or None
+    (zeros, no gradient): the input applied where the first filter call fails.  xlog [T,nx,B] holds the state each call
+    saw, ulog [T,nu,B] the input applied after it; rclog int32 [T,B] and nfail int32 [B] are not differentiable.
+    Gradients flow to x0, udes and uact_prev from xT, uactT, xlog and ulog.  Forward is one asif_hip_rollout_batch launch
+    with all three logs, backward one asif_hip_rollout_vjp_batch launch on them; gradients of outputs the caller did not
+    use are handed to it as NULL.  To change udes along a trajectory, chain segments: xT and uactT feed the next one."""
+
+    @staticmethod
+    def forward(ctx, flt, x0, udes, uact_prev, T, dt):
+        d = flt.dims
+        B = x0.shape[1]
+        T = int(T)
+        if T < 0:
+            raise ValueError(f"T: expected a non-negative step count, got {T}")
+        if flt.model != capi.MODEL_DOUBLE_INTEGRATOR or flt.variant != capi.EXPLICIT:
+            raise ValueError("the differentiable rollout exists for the explicit filter on the double integrator only")
+        x = _soa(x0, d.nx, B, "x0").clone()
+        udes = _soa(udes, d.nu, B, "udes")
+        uact = (_soa(uact_prev, d.nu, B, "uact_prev").clone() if uact_prev is not None
+                else torch.zeros((d.nu, B), dtype=torch.float64, device=x.device))
+        relax = torch.zeros((d.nrelax, B), dtype=torch.float64, device=x.device)
+        nfail = torch.zeros(B, dtype=torch.int32, device=x.device)
+        xlog = torch.zeros((T, d.nx, B), dtype=torch.float64, device=x.device)
+        ulog = torch.zeros((T, d.nu, B), dtype=torch.float64, device=x.device)
+        rclog = torch.zeros((T, B), dtype=torch.int32, device=x.device)
+        if B > 0 and T > 0:
+            flt.rollout(T, float(dt), x, udes, uact, relax, nfail, xlog, ulog, rclog)
+        ctx.flt, ctx.T, ctx.dt = flt, T, float(dt)
+        ctx.save_for_backward(xlog, ulog, rclog, udes)
+        ctx.mark_non_differentiable(rclog, nfail)
+        ctx.set_materialize_grads(False)
+        return x, uact, xlog, ulog, rclog, nfail
+
+    @staticmethod
+    def backward(ctx, gxT, guactT, gxlog, gulog, _grclog, _gnfail):
+        xlog, ulog, rclog, udes = ctx.saved_tensors
+        need = ctx.needs_input_grad[1:4]
+        given = [g for g in (gxT, guactT, gxlog, gulog) if g is not None]
+        if not any(need) or not given:  # nothing asked for, or no output was used: nothing to launch
+            return None, None, None, None, None, None
+        d = ctx.flt.dims
+        B = udes.shape[1]
+        cont = lambda g: None if g is None else g.contiguous()
+        gxT = cont(gxT) if gxT is not None else torch.zeros((d.nx, B), dtype=torch.float64, device=udes.device)
+        gx0 = torch.empty((d.nx, B), dtype=torch.float64, device=udes.device)
+        gudes, guact0 = torch.empty_like(udes), torch.empty_like(udes)
+        if B > 0:
+            ctx.flt.rollout_vjp(ctx.T, ctx.dt, xlog, ulog, rclog, udes, gxT, gx0, gudes, guact0,
+                                torch.empty(B, dtype=torch.int32, device=udes.device), guactT=cont(guactT),
+                                gxlog=cont(gxlog) if ctx.T > 0 else None, gulog=cont(gulog) if ctx.T > 0 else None)
+        return (None, gx0 if need[0] else None, gudes if need[1] else None, guact0 if need[2] else None, None, None)
+
+
+class ExplicitRolloutLayer(torch.nn.Module):
+    """Owns an explicit capi.Filter and rolls the closed loop out for T steps of dt with udes held:
+    xT, uactT, xlog, ulog, rclog, nfail = layer(x0, udes[, uact_prev])."""
+
+    def __init__(self, model=capi.MODEL_DOUBLE_INTEGRATOR, options=None, solver=None, device=0, T=1, dt=1e-3):
+        super().__init__()
+        self.filter = capi.Filter(model, capi.EXPLICIT, options=options, solver=solver, device=device)
+        self.T, self.dt = int(T), float(dt)
+
+    def forward(self, x0, udes, uact_prev=None):
+        return ExplicitRolloutFn.apply(self.filter, x0, udes, uact_prev, self.T, self.dt)
 
 
 class QPSolveFn(torch.autograd.Function):

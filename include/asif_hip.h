@@ -48,14 +48,16 @@
 extern "C" {
 #endif
 
-#define ASIF_HIP_VERSION 150 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
+#define ASIF_HIP_VERSION 160 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
                               * 120: ASIF_HIP_IMPLICIT_RB (options grew at the end), asif_hip_set_learning, asif_hip_affine_replay;
                               * 130: solver.adaptive_rho_interval (struct grew at the end), polish == 2 is the dual active-set
                               *      stage of gi_small.hpp;
                               * 131: that stage eliminates variables pinned by their bounds and solves one-variable problems in
                               *      closed form; class ASIF with one input runs on a kernel without the iterative stages;
                               * 140: asif_hip_filter_vjp_batch, the explicit filter's vector-Jacobian product;
-                              * 150: asif_hip_qp_vjp_batch, the vector-Jacobian product of the in-register QP solve */
+                              * 150: asif_hip_qp_vjp_batch, the vector-Jacobian product of the in-register QP solve;
+                              * 160: asif_hip_rollout_vjp_batch, the fused explicit rollout backwards (with the model's second
+                              *      derivatives: a state gradient on the model's own Lie derivatives) */
 
 enum asif_hip_error {
 	ASIF_HIP_OK = 0,
@@ -334,6 +336,40 @@ int asif_hip_filter_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const d
 int asif_hip_rollout_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, double *x,
                            const double *udes, double *uact, double *relax, int32_t *nfail, double *xlog,
                            double *ulog, int32_t *rclog, void *stream);
+
+/* The fused explicit rollout backwards (class ASIF on ASIF_HIP_MODEL_DOUBLE_INTEGRATOR; no counterpart in the reference):
+ * the gradient of a scalar loss L through T x (filter + plant Euler step), in one launch.  The forward pass is, for
+ * t = 0 ... T-1 with u_{-1} the uact handed in,
+ *     xlog[t] = x_t;   (ok_t, u*_t) = filter(x_t, udes);   u_t = ok_t ? u*_t : u_{t-1};   ulog[t] = u_t;
+ *     rclog[t] = ok_t ? 1 : -1;   x_{t+1} = x_t + dt (f(x_t) + g(x_t) u_t)
+ * with outputs x_T and uact = u_{T-1}; relax is the pinned constant relaxLb and takes no gradient.  The sweep starts from
+ * lambda = gxT, mu = guactT, gudes = 0 and runs t = T-1 ... 0:
+ *     mu      += gulog[t] + dt g(x_t)' lambda
+ *     lambda'  = lambda + dt (Df(x_t) + sum_j u_t,j Dg_j(x_t))' lambda + gxlog[t]
+ *     rclog[t] == 1:  the step's forward solve is repeated on x_t = xlog[t] (same rows, same row selection under npSSmax)
+ *                     and, with W its working set and gbar = mu, the adjoint of asif_hip_filter_vjp_batch gives
+ *                         gudes   += 2 z
+ *                         lambda' += Dh' gh + (dLfh/dx)' glfh + (dLgh/dx)' glgh,    mu = 0
+ *                     where dLfh_r/dx_m = sum_k (D2h_r[k,m] f_k + Dh_r[k] Df[k,m]) and
+ *                     dLgh_{r,j}/dx_m = sum_k (D2h_r[k,m] g_{k,j} + Dh_r[k] Dg_j[k,m]): the model's second derivatives
+ *     otherwise:      mu passes on unchanged (the step kept u_{t-1})
+ *     lambda = lambda'
+ * and ends with gx0 = lambda, guact0 = mu.  Kinks (the branch of the safety set, the row order under npSSmax, a constraint
+ * met with equality but outside W, the clamp) are taken on the side the forward pass took.
+ *   xlog[T][nx][ldx], ulog[T][nu][ldx], rclog[T][ldx]: what asif_hip_rollout_batch logged (may be NULL when T == 0);
+ *   udes[nu][ldx] as handed to it.  rclog is the caller's record of the forward pass: a step with rclog[t] != 1 carries
+ *   mu whatever the kernel's own solve says; a step with rclog[t] == 1 whose repeated solve does not end optimal (it is
+ *   the same code on the same bits: not on logs this library wrote) sets mu = 0, adds nothing and is counted in nskip.
+ *   gxT[nx][ldx] in;  guactT[nu][ldx], gxlog[T][nx][ldx], gulog[T][nu][ldx] in, each may be NULL (zero).
+ *   gx0[nx][ldx], gudes[nu][ldx], guact0[nu][ldx], nskip int32[B] out: every slot of every instance i < B is written.
+ *   T == 0 is the identity: gx0 = gxT, guact0 = guactT (or 0), gudes = 0, nskip = 0.  B == 0 returns ASIF_HIP_OK.
+ * Explicit handles on DOUBLE_INTEGRATOR in the default solver mode (polish == 2, with or without presolve; lanes_per_qp
+ * 0 or 1), any npSSmax; anything else: ASIF_HIP_EUNSUPPORTED.  A NULL required pointer, ldx < B, T < 0 or B < 0:
+ * ASIF_HIP_EINVAL.  The handle's forward results do not change. */
+int asif_hip_rollout_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, const double *xlog,
+                               const double *ulog, const int32_t *rclog, const double *udes, const double *gxT,
+                               const double *guactT, const double *gxlog, const double *gulog, double *gx0,
+                               double *gudes, double *guact0, int32_t *nskip, void *stream);
 
 /* Rows only: A[(nc*nv)][ldx], b[nc][ldx], code[B] (1; TB: 2 trivial rows, -3 backup set unreached). */
 int asif_hip_assemble_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, double *A, double *b,
