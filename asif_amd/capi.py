@@ -50,6 +50,7 @@ EXPORTS = [
     "asif_hip_multi_handle", "asif_hip_multi_update_options", "asif_hip_filter_batch_host_multi",
     "asif_hip_filter_batch_lie", "asif_hip_filter_vjp_batch",
     "asif_hip_math_probe", "asif_hip_qp_solve_batch_warm", "asif_hip_qp_vjp_batch", "asif_hip_rollout_vjp_batch",
+    "asif_hip_rollout_policy_batch", "asif_hip_rollout_policy_vjp_batch",
 ]
 
 MODEL_DOUBLE_INTEGRATOR_SAMPLED = 4
@@ -169,6 +170,8 @@ def load():
         lib.asif_hip_filter_vjp_batch.argtypes = [vp, i64, i64] + [vp] * 11
         lib.asif_hip_qp_vjp_batch.argtypes = [C.c_int, i64, i64, C.c_int32, C.c_int32] + [vp] * 17
         lib.asif_hip_rollout_vjp_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double] + [vp] * 13
+        lib.asif_hip_rollout_policy_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double] + [vp] * 11
+        lib.asif_hip_rollout_policy_vjp_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double] + [vp] * 17
         _lib = lib
     return _lib
 
@@ -280,6 +283,27 @@ class Filter:
                                                   _ptr(rclog), _ptr(udes), _ptr(gxT), _ptr(guactT), _ptr(gxlog),
                                                   _ptr(gulog), _ptr(gx0), _ptr(gudes), _ptr(guact0), _ptr(nskip),
                                                   _stream()))
+
+    def rollout_policy(self, T, dt, x, k, uact, relax, nfail, K=None, v=None, xlog=None, ulog=None, rclog=None):
+        """The fused explicit rollout under the affine policy uDes_t = k + K x_t + v_t (asif_hip_rollout_policy_batch),
+        one launch: k [nu,B]; K [nu*nx,B] (entry (j, m) at component j + m*nu) and v [T,nu,B] each optional; the rest as
+        rollout().  x, uact, relax are updated in place."""
+        B = x.shape[1]
+        check(self.lib.asif_hip_rollout_policy_batch(self.handle, B, x.stride(0), T, dt, _ptr(x), _ptr(K), _ptr(k),
+                                                     _ptr(v), _ptr(uact), _ptr(relax), _ptr(nfail), _ptr(xlog),
+                                                     _ptr(ulog), _ptr(rclog), _stream()))
+
+    def rollout_policy_vjp(self, T, dt, xlog, ulog, rclog, k, gxT, gx0, gk, guact0, nskip, K=None, v=None, guactT=None,
+                           gxlog=None, gulog=None, gK=None, gv=None):
+        """rollout_policy() backwards (asif_hip_rollout_policy_vjp_batch), one launch: the logs as rollout_policy() wrote
+        them, k, K, v as handed to it; gxT [nx,B] and, each optional, guactT [nu,B], gxlog, gulog (shaped like the logs)
+        in; gx0 [nx,B], gk [nu,B], guact0 [nu,B], nskip int32[B] and, each optional, gK (like K), gv (like v) out.  Every
+        tensor shares gxT's leading dimension."""
+        B = gxT.shape[1]
+        check(self.lib.asif_hip_rollout_policy_vjp_batch(self.handle, B, gxT.stride(0), T, dt, _ptr(xlog), _ptr(ulog),
+                                                         _ptr(rclog), _ptr(K), _ptr(k), _ptr(v), _ptr(gxT),
+                                                         _ptr(guactT), _ptr(gxlog), _ptr(gulog), _ptr(gx0), _ptr(gK),
+                                                         _ptr(gk), _ptr(gv), _ptr(guact0), _ptr(nskip), _stream()))
 
     def assemble(self, x, A, b, code, diag=None):
         B = x.shape[1]

@@ -83,6 +83,31 @@ struct RolloutVjpArgs {
 	int32_t *nskip;               // [B] steps with rclog == 1 that the kernel's own solve did not decide
 };
 int launch_rollout_vjp_explicit_di(const DevOptions &o, const RolloutVjpArgs &a, hipStream_t stream);
+// the fused explicit rollout under an affine policy uDes_t = k + K x_t + v_t and its adjoint (k_rollout_policy.hip)
+struct PolicyRolloutArgs {
+	int64_t B, ld;
+	int T;
+	double dt;
+	double *x;                 // [nx][ld] in: initial state, out: state after T steps
+	const double *K, *k, *v;   // [nu*nx][ld] entry (j, m) at j + m nu, or nullptr; [nu][ld]; [T][nu][ld], or nullptr
+	double *uact, *relax;      // as RolloutArgs
+	int32_t *nfail;            // [B]
+	double *xlog, *ulog;       // as RolloutArgs, each may be nullptr
+	int32_t *rclog;
+};
+int launch_rollout_policy_explicit_di(const DevOptions &o, const PolicyRolloutArgs &a, hipStream_t stream);
+struct PolicyRolloutVjpArgs {
+	int64_t B, ld;
+	int T;
+	double dt;
+	const double *xlog, *ulog; // as RolloutVjpArgs
+	const int32_t *rclog;
+	const double *K, *k, *v;   // as PolicyRolloutArgs
+	const double *gxT, *guactT, *gxlog, *gulog; // as RolloutVjpArgs
+	double *gx0, *gK, *gk, *gv, *guact0; // [nx][ld]; [nu*nx][ld] or nullptr; [nu][ld]; [T][nu][ld] or nullptr; [nu][ld]
+	int32_t *nskip;                      // [B]
+};
+int launch_rollout_policy_vjp_explicit_di(const DevOptions &o, const PolicyRolloutVjpArgs &a, hipStream_t stream);
 // plant Euler step x += dt (f(x) + g(x) uact) between two filter calls of the two-stage filters (k_rollout.hip);
 // logs the state / input / rc of the call just made (nullptr to skip) and counts rc < 0 into nfail
 int launch_plant_step(int model, const DevOptions &o, int64_t B, int64_t ld, double dt, double *x, const double *uact,

@@ -4,6 +4,8 @@ The explicit safety filter (class ASIF).  Forward: asif_hip_filter_batch / asif_
 asif_hip_filter_vjp_batch launch (asif_amd/csrc/k_explicit_vjp.hip).
 The fused explicit rollout, T x (filter + plant Euler step) on the double integrator.  Forward: asif_hip_rollout_batch.
 Backward: one asif_hip_rollout_vjp_batch launch (asif_amd/csrc/k_rollout_vjp.hip), state gradient included.
+The same rollout under an affine policy udes_t = k + K x_t + v_t evaluated inside the loop.  Forward:
+asif_hip_rollout_policy_batch.  Backward: one asif_hip_rollout_policy_vjp_batch launch (asif_amd/csrc/k_rollout_policy.hip).
 The batched solve of small pre-assembled QPs.  Forward: asif_hip_qp_solve_batch.  Backward: one asif_hip_qp_vjp_batch
 launch (asif_amd/csrc/k_qp_vjp.hip).
 All of it runs on torch's current stream; nothing here computes on the CPU, and no solve or adjoint falls back to torch
@@ -99,7 +101,8 @@ class ExplicitRolloutFn(torch.autograd.Function):
     saw, ulog [T,nu,B] the input applied after it; rclog int32 [T,B] and nfail int32 [B] are not differentiable.
     Gradients flow to x0, udes and uact_prev from xT, uactT, xlog and ulog.  Forward is one asif_hip_rollout_batch launch
     with all three logs, backward one asif_hip_rollout_vjp_batch launch on them; gradients of outputs the caller did not
-    use are handed to it as NULL.  To change udes along a trajectory, chain segments: xT and uactT feed the next one."""
+    use are handed to it as NULL.  To change udes along a trajectory -- state feedback, a planned input sequence -- use
+    PolicyRolloutFn / PolicyRolloutLayer: the same rollout with udes_t = k + K x_t + v_t evaluated inside the launch."""
 
     @staticmethod
     def forward(ctx, flt, x0, udes, uact_prev, T, dt):
@@ -158,6 +161,90 @@ class ExplicitRolloutLayer(torch.nn.Module):
 
     def forward(self, x0, udes, uact_prev=None):
         return ExplicitRolloutFn.apply(self.filter, x0, udes, uact_prev, self.T, self.dt)
+
+
+class PolicyRolloutFn(torch.autograd.Function):
+    """xT, uactT, xlog, ulog, rclog, nfail = PolicyRolloutFn.apply(flt, x0, k, K, v, uact_prev, T, dt)
+
+    ExplicitRolloutFn with the desired input coming from an affine policy evaluated inside the loop:
+    udes_t = k + K x_t + v_t.  k [nu,B]; K [nu*nx,B] (entry (j, m) of an instance's gain at component j + m*nu) or None;
+    v [T,nu,B] (a planned input sequence) or None; an absent term is not evaluated.  uact_prev and the outputs as
+    ExplicitRolloutFn.  Gradients flow to x0, k, K, v and uact_prev from xT, uactT, xlog and ulog.  Forward is one
+    asif_hip_rollout_policy_batch launch with all three logs, backward one asif_hip_rollout_policy_vjp_batch launch on
+    them; gradients of outputs the caller did not use are handed to it as NULL, and gK / gv are asked for only where K / v
+    require a gradient.  A gain shared by the batch is K.expand(-1, B) of a [nu*nx,1] parameter: autograd's own sum over
+    the expanded axis turns the per-instance gK into the shared gain's gradient (likewise k and v).
+    The policy's output is not returned: udes_t = k + K xlog[t] + v[t] in torch, and gxlog carries its state part back."""
+
+    @staticmethod
+    def forward(ctx, flt, x0, k, K, v, uact_prev, T, dt):
+        d = flt.dims
+        B = x0.shape[1]
+        T = int(T)
+        if T < 0:
+            raise ValueError(f"T: expected a non-negative step count, got {T}")
+        if flt.model != capi.MODEL_DOUBLE_INTEGRATOR or flt.variant != capi.EXPLICIT:
+            raise ValueError("the differentiable rollout exists for the explicit filter on the double integrator only")
+        x = _soa(x0, d.nx, B, "x0").clone()
+        k = _soa(k, d.nu, B, "k")
+        K = _soa(K, d.nu * d.nx, B, "K") if K is not None else None
+        if v is not None:
+            if v.dim() != 3 or v.shape[0] != T:
+                raise ValueError(f"v: expected shape ({T}, {d.nu}, {B}), got {tuple(v.shape)}")
+            v = _soa(v.reshape(T * d.nu, B), T * d.nu, B, "v").reshape(T, d.nu, B)
+        uact = (_soa(uact_prev, d.nu, B, "uact_prev").clone() if uact_prev is not None
+                else torch.zeros((d.nu, B), dtype=torch.float64, device=x.device))
+        relax = torch.zeros((d.nrelax, B), dtype=torch.float64, device=x.device)
+        nfail = torch.zeros(B, dtype=torch.int32, device=x.device)
+        xlog = torch.zeros((T, d.nx, B), dtype=torch.float64, device=x.device)
+        ulog = torch.zeros((T, d.nu, B), dtype=torch.float64, device=x.device)
+        rclog = torch.zeros((T, B), dtype=torch.int32, device=x.device)
+        if B > 0 and T > 0:
+            flt.rollout_policy(T, float(dt), x, k, uact, relax, nfail, K=K, v=v, xlog=xlog, ulog=ulog, rclog=rclog)
+        ctx.flt, ctx.T, ctx.dt, ctx.hasK, ctx.hasV = flt, T, float(dt), K is not None, v is not None
+        ctx.save_for_backward(xlog, ulog, rclog, k, *(t for t in (K, v) if t is not None))
+        ctx.mark_non_differentiable(rclog, nfail)
+        ctx.set_materialize_grads(False)
+        return x, uact, xlog, ulog, rclog, nfail
+
+    @staticmethod
+    def backward(ctx, gxT, guactT, gxlog, gulog, _grclog, _gnfail):
+        xlog, ulog, rclog, k = ctx.saved_tensors[:4]
+        rest = list(ctx.saved_tensors[4:])
+        K = rest.pop(0) if ctx.hasK else None
+        v = rest.pop(0) if ctx.hasV else None
+        need = ctx.needs_input_grad[1:6]  # x0, k, K, v, uact_prev
+        given = [g for g in (gxT, guactT, gxlog, gulog) if g is not None]
+        if not any(need) or not given:  # nothing asked for, or no output was used: nothing to launch
+            return (None,) * 8
+        d = ctx.flt.dims
+        B, T = k.shape[1], ctx.T
+        cont = lambda g: None if g is None else g.contiguous()
+        gxT = cont(gxT) if gxT is not None else torch.zeros((d.nx, B), dtype=torch.float64, device=k.device)
+        gx0 = torch.empty((d.nx, B), dtype=torch.float64, device=k.device)
+        gk, guact0 = torch.empty_like(k), torch.empty_like(k)
+        gK = torch.empty_like(K) if ctx.hasK and need[2] else None
+        gv = torch.empty_like(v) if ctx.hasV and need[3] else None
+        if B > 0:
+            steps = T > 0  # without a step there is no log, no v and no gv to hand over
+            ctx.flt.rollout_policy_vjp(T, ctx.dt, xlog, ulog, rclog, k, gxT, gx0, gk, guact0,
+                                       torch.empty(B, dtype=torch.int32, device=k.device), K=K, v=v if steps else None,
+                                       guactT=cont(guactT), gxlog=cont(gxlog) if steps else None,
+                                       gulog=cont(gulog) if steps else None, gK=gK, gv=gv if steps else None)
+        return (None, gx0 if need[0] else None, gk if need[1] else None, gK, gv, guact0 if need[4] else None, None, None)
+
+
+class PolicyRolloutLayer(torch.nn.Module):
+    """Owns an explicit capi.Filter and rolls the closed loop out for T steps of dt under udes_t = k + K x_t + v_t:
+    xT, uactT, xlog, ulog, rclog, nfail = layer(x0, k, K=None, v=None, uact_prev=None)."""
+
+    def __init__(self, model=capi.MODEL_DOUBLE_INTEGRATOR, options=None, solver=None, device=0, T=1, dt=1e-3):
+        super().__init__()
+        self.filter = capi.Filter(model, capi.EXPLICIT, options=options, solver=solver, device=device)
+        self.T, self.dt = int(T), float(dt)
+
+    def forward(self, x0, k, K=None, v=None, uact_prev=None):
+        return PolicyRolloutFn.apply(self.filter, x0, k, K, v, uact_prev, self.T, self.dt)
 
 
 class QPSolveFn(torch.autograd.Function):

@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define ASIF_HIP_VERSION 160 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
+#define ASIF_HIP_VERSION 170 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
                               * 120: ASIF_HIP_IMPLICIT_RB (options grew at the end), asif_hip_set_learning, asif_hip_affine_replay;
                               * 130: solver.adaptive_rho_interval (struct grew at the end), polish == 2 is the dual active-set
                               *      stage of gi_small.hpp;
@@ -57,7 +57,9 @@ extern "C" {
                               * 140: asif_hip_filter_vjp_batch, the explicit filter's vector-Jacobian product;
                               * 150: asif_hip_qp_vjp_batch, the vector-Jacobian product of the in-register QP solve;
                               * 160: asif_hip_rollout_vjp_batch, the fused explicit rollout backwards (with the model's second
-                              *      derivatives: a state gradient on the model's own Lie derivatives) */
+                              *      derivatives: a state gradient on the model's own Lie derivatives);
+                              * 170: asif_hip_rollout_policy_batch / asif_hip_rollout_policy_vjp_batch, the fused explicit rollout
+                              *      and its adjoint under an affine policy uDes_t = k + K x_t + v_t evaluated inside the loop */
 
 enum asif_hip_error {
 	ASIF_HIP_OK = 0,
@@ -370,6 +372,41 @@ int asif_hip_rollout_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_
                                const double *ulog, const int32_t *rclog, const double *udes, const double *gxT,
                                const double *guactT, const double *gxlog, const double *gulog, double *gx0,
                                double *gudes, double *guact0, int32_t *nskip, void *stream);
+
+/* The fused explicit rollout under an affine policy (class ASIF on ASIF_HIP_MODEL_DOUBLE_INTEGRATOR; no counterpart in the
+ * reference): asif_hip_rollout_batch's fused path with the desired input evaluated inside the loop.  For t = 0 ... T-1,
+ * with u_{-1} the uact handed in,
+ *     uDes_t = k + K x_t + v_t;   (ok_t, u*_t) = filter(x_t, uDes_t);   u_t = ok_t ? u*_t : u_{t-1};
+ *     x_{t+1} = x_t + dt (f(x_t) + g(x_t) u_t)
+ * uDes_t,j is formed in one order, without contraction: k_j, plus K[j,m] x_t,m for m = 0 ... nx-1, plus v_t,j.
+ *   K[nu*nx][ldx], entry (j, m) at component j + m nu: per-instance feedback gains, or NULL;  k[nu][ldx];
+ *   v[T][nu][ldx]: a planned input sequence, or NULL.  A NULL term is not evaluated at all: with K = v = NULL every output
+ *   equals asif_hip_rollout_batch's with udes = k, bit for bit.
+ *   x, uact, relax, nfail, xlog, ulog, rclog: as asif_hip_rollout_batch (the three logs may be NULL).
+ * Explicit handles on DOUBLE_INTEGRATOR whose solver mode is the dual active-set stage (polish == 2, or presolve;
+ * lanes_per_qp 0 or 1), any npSSmax; anything else: ASIF_HIP_EUNSUPPORTED.  A NULL required pointer, ldx < B, T < 0 or
+ * B < 0: ASIF_HIP_EINVAL.  B == 0 or T == 0 returns ASIF_HIP_OK and touches nothing. */
+int asif_hip_rollout_policy_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, double *x,
+                                  const double *K, const double *k, const double *v, double *uact, double *relax,
+                                  int32_t *nfail, double *xlog, double *ulog, int32_t *rclog, void *stream);
+
+/* asif_hip_rollout_policy_batch backwards, in one launch: the sweep of asif_hip_rollout_vjp_batch with uDes_t recomputed
+ * from xlog[t] (the forward pass's bits) and each step's own d_t = dL/duDes_t -- mu on a step that ends free, zero on a
+ * failed step and on one that ends on a row or a bound -- distributed as
+ *     gk += d_t;   gK[j,m] += d_t[j] x_t[m];   gv[t] = d_t;   lambda += K' d_t
+ * where lambda is the value the step leaves for t-1.
+ *   xlog, ulog, rclog: what the forward entry logged (may be NULL when T == 0);  K, k, v: as handed to it.
+ *   gxT[nx][ldx] in;  guactT[nu][ldx], gxlog[T][nx][ldx], gulog[T][nu][ldx] in, each may be NULL (zero).
+ *   gx0[nx][ldx], gk[nu][ldx], guact0[nu][ldx], nskip int32[B] out;  gK[nu*nx][ldx], gv[T][nu][ldx] out, each may be NULL
+ *   (not wanted).  gK without K or gv without v: ASIF_HIP_EINVAL.  Every slot of every instance i < B is written.
+ *   T == 0 is the identity: gx0 = gxT, guact0 = guactT (or 0), gk = gK = 0, nskip = 0, gv untouched.
+ * Handles, refusals and nskip as asif_hip_rollout_vjp_batch.  With K = v = NULL, gx0, guact0, nskip and gk equal that
+ * entry's gx0, guact0, nskip and gudes bit for bit.  The handle's forward results do not change. */
+int asif_hip_rollout_policy_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, const double *xlog,
+                                      const double *ulog, const int32_t *rclog, const double *K, const double *k,
+                                      const double *v, const double *gxT, const double *guactT, const double *gxlog,
+                                      const double *gulog, double *gx0, double *gK, double *gk, double *gv,
+                                      double *guact0, int32_t *nskip, void *stream);
 
 /* Rows only: A[(nc*nv)][ldx], b[nc][ldx], code[B] (1; TB: 2 trivial rows, -3 backup set unreached). */
 int asif_hip_assemble_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, double *A, double *b,
