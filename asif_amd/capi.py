@@ -51,6 +51,7 @@ EXPORTS = [
     "asif_hip_filter_batch_lie", "asif_hip_filter_vjp_batch",
     "asif_hip_math_probe", "asif_hip_qp_solve_batch_warm", "asif_hip_qp_vjp_batch", "asif_hip_rollout_vjp_batch",
     "asif_hip_rollout_policy_batch", "asif_hip_rollout_policy_vjp_batch",
+    "asif_hip_rollout_params_batch", "asif_hip_rollout_params_vjp_batch",
 ]
 
 MODEL_DOUBLE_INTEGRATOR_SAMPLED = 4
@@ -172,6 +173,8 @@ def load():
         lib.asif_hip_rollout_vjp_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double] + [vp] * 13
         lib.asif_hip_rollout_policy_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double] + [vp] * 11
         lib.asif_hip_rollout_policy_vjp_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double] + [vp] * 17
+        lib.asif_hip_rollout_params_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double] + [vp] * 14
+        lib.asif_hip_rollout_params_vjp_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double] + [vp] * 23
         _lib = lib
     return _lib
 
@@ -304,6 +307,28 @@ class Filter:
                                                          _ptr(rclog), _ptr(K), _ptr(k), _ptr(v), _ptr(gxT),
                                                          _ptr(guactT), _ptr(gxlog), _ptr(gulog), _ptr(gx0), _ptr(gK),
                                                          _ptr(gk), _ptr(gv), _ptr(guact0), _ptr(nskip), _stream()))
+
+    def rollout_params(self, T, dt, x, k, uact, relax, nfail, K=None, v=None, alpha=None, lb=None, ub=None, xlog=None,
+                       ulog=None, rclog=None):
+        """rollout_policy() with the barrier gain alpha [B] (options.relaxLb) and the input box lb, ub [nu,B] per
+        instance (asif_hip_rollout_params_batch), one launch; each of the three optional: None is the handle's value."""
+        B = x.shape[1]
+        check(self.lib.asif_hip_rollout_params_batch(self.handle, B, x.stride(0), T, dt, _ptr(x), _ptr(K), _ptr(k),
+                                                     _ptr(v), _ptr(alpha), _ptr(lb), _ptr(ub), _ptr(uact), _ptr(relax),
+                                                     _ptr(nfail), _ptr(xlog), _ptr(ulog), _ptr(rclog), _stream()))
+
+    def rollout_params_vjp(self, T, dt, xlog, ulog, rclog, k, gxT, gx0, gk, guact0, nskip, K=None, v=None, alpha=None,
+                           lb=None, ub=None, guactT=None, gxlog=None, gulog=None, gK=None, gv=None, galpha=None,
+                           glb=None, gub=None):
+        """rollout_params() backwards (asif_hip_rollout_params_vjp_batch), one launch: rollout_policy_vjp()'s arguments,
+        alpha, lb, ub as handed to rollout_params() and, each optional, galpha [B], glb, gub [nu,B] out (only for a
+        parameter that was given)."""
+        B = gxT.shape[1]
+        check(self.lib.asif_hip_rollout_params_vjp_batch(self.handle, B, gxT.stride(0), T, dt, _ptr(xlog), _ptr(ulog),
+                                                         _ptr(rclog), _ptr(K), _ptr(k), _ptr(v), _ptr(alpha), _ptr(lb),
+                                                         _ptr(ub), _ptr(gxT), _ptr(guactT), _ptr(gxlog), _ptr(gulog),
+                                                         _ptr(gx0), _ptr(gK), _ptr(gk), _ptr(gv), _ptr(galpha),
+                                                         _ptr(glb), _ptr(gub), _ptr(guact0), _ptr(nskip), _stream()))
 
     def assemble(self, x, A, b, code, diag=None):
         B = x.shape[1]

@@ -1,0 +1,308 @@
+// k_rollout_params.hip -- the fused explicit rollout under an affine policy (k_rollout_policy.hip) with the filter's own
+// parameters per instance, and its adjoint:
+//     uDes_t = k + K x_t + v_t;   (ok_t, u*_t) = filter(x_t, uDes_t; alpha_i, lb_i, ub_i);   u_t = ok_t ? u*_t : u_{t-1};
+//     x_{t+1} = x_t + dt (f(x_t) + g(x_t) u_t)
+// alpha (the barrier gain: DevOptions::relaxLb), lb and ub are each optional; an absent one is the handle's value in every
+// lane.  Without all three the forward kernel computes what rollout_policy_kernel computes, bit for bit, and the backward
+// kernel what rollout_policy_vjp_kernel computes.
+//
+// Forward: rollout_policy_kernel's structure -- one instance per lane, 256-thread workgroups, x / uAct / K / k and the
+// three parameters in registers for the whole rollout, v_{t+1} loaded behind step t's solve and waited for in front of
+// step t's stores.  The row assembly and the plant step restate that kernel's.
+// Backward: rollout_policy_vjp_kernel's structure around rollout_params_step.hpp; lambda, mu, gk, gK, galpha, glb, gub in
+// registers.  WANTP (one of the three gradients is asked for) is a template argument: without it the loop is
+// rollout_policy_vjp_kernel's.
+// HBM traffic on top of k_rollout_policy.hip's, per instance and LAUNCH: 8 bytes read per parameter given, 8 written per
+// gradient asked for.  SoA, every load and store a coalesced line; no LDS, no scratch, no register array indexed by a
+// run-time value.  Lanes beyond B repeat instance B-1 for the solver's votes and never store.
+#include <cstdint>
+#include "launchers.hpp"
+#include "rollout_params_step.hpp"
+
+namespace asif {
+
+// see k_rollout_policy.hip: the wait for a load issued earlier is placed here
+__device__ __forceinline__ void arrived_p(double &r) { asm volatile("" : "+v"(r)); }
+
+// the handle's fields, then the instance's own where given; gainOk: param_gain_usable of a gain that was handed in
+template <class M>
+__device__ __forceinline__ RolloutVjpOpts<M::NU> lane_opts(const RolloutVjpOpts<M::NU> &e, const double *alpha,
+                                                          const double *lb, const double *ub, int64_t ld, int64_t i,
+                                                          bool &gainOk)
+{
+	RolloutVjpOpts<M::NU> el = e;
+	if (alpha) el.relaxLb = alpha[i]; // wave-uniform, as the two below
+#pragma unroll
+	for (int j = 0; j < M::NU; j++) {
+		if (lb) el.lb[j] = lb[j * ld + i];
+		if (ub) el.ub[j] = ub[j * ld + i];
+	}
+	gainOk = alpha ? param_gain_usable(el.relaxLb) : true;
+	return el;
+}
+
+template <class M, bool HASV>
+__global__ __launch_bounds__(256) void rollout_params_kernel(RolloutVjpOpts<M::NU> e, ParamRolloutArgs pa)
+{
+	static_assert(M::kIgnoresOptions, "the model's functors must not read DevOptions: only the class's fields are passed");
+	static_assert(M::NU == 1, "one input: the pinned relaxation variable leaves a one-variable problem");
+	constexpr int NX = M::NX, NU = M::NU, NP = M::NPSS, NV = NU + 1, NC = NP;
+	const PolicyRolloutArgs &a = pa.p;
+	const DevOptions o = {};
+	int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const bool live = i < a.B;
+	if (!live) i = a.B - 1; // keep the lane in the wave votes of the solve; it never stores
+	const int64_t ld = a.ld;
+	const bool hasK = a.K != nullptr; // wave-uniform
+	constexpr bool hasV = HASV;
+	bool gainOk;
+	RolloutVjpOpts<NU> el = lane_opts<M>(e, pa.alpha, pa.lb, pa.ub, ld, i, gainOk);
+	double x[NX], uAct[NU], kk[NU], K[NU * NX], v[NU], vn[NU], relax;
+#pragma unroll
+	for (int k = 0; k < NX; k++) x[k] = a.x[k * ld + i];
+#pragma unroll
+	for (int j = 0; j < NU; j++) {
+		kk[j] = a.k[j * ld + i];
+		uAct[j] = a.uact[j * ld + i];
+		v[j] = hasV ? a.v[j * ld + i] : 0.0; // T >= 1: the launcher does not launch otherwise
+		vn[j] = 0.0;
+	}
+#pragma unroll
+	for (int c = 0; c < NU * NX; c++) K[c] = hasK ? a.K[c * ld + i] : 0.0;
+	relax = a.relax[i];
+	int nfail = 0;
+	if constexpr (HASV) { // the launch's own loads end here: a wait left at the loop's head would cover each step's stores
+#pragma unroll
+		for (int k = 0; k < NX; k++) arrived_p(x[k]);
+#pragma unroll
+		for (int j = 0; j < NU; j++) arrived_p(kk[j]), arrived_p(uAct[j]), arrived_p(v[j]), arrived_p(el.lb[j]), arrived_p(el.ub[j]);
+#pragma unroll
+		for (int c = 0; c < NU * NX; c++) arrived_p(K[c]);
+		arrived_p(relax);
+		arrived_p(el.relaxLb);
+	}
+#pragma unroll 1
+	for (int t = 0; t < a.T; t++) { // wave-uniform trip count
+		if (hasV && t + 1 < a.T) {
+#pragma unroll
+			for (int j = 0; j < NU; j++) vn[j] = a.v[((int64_t)(t + 1) * NU + j) * ld + i]; // in flight behind this step's solve
+		}
+		double uDes[NU];
+		policy_udes<NX, NU>(kk, K, hasK, x, v, hasV, uDes);
+		double h[NP], Dh[NP * NX], f[NX], gm[NX * NU];
+		M::safetySet(o, x, h, Dh);
+		M::dynamics(o, x, f, gm);
+		QpLaneData<NV, NC> qp;
+#pragma unroll
+		for (int r = 0; r < NP; r++) {
+			double s = 0.0;
+#pragma unroll
+			for (int k = 0; k < NX; k++) s += Dh[r + k * NP] * f[k];
+#pragma unroll
+			for (int j = 0; j < NU; j++) {
+				double tt = 0.0;
+#pragma unroll
+				for (int k = 0; k < NX; k++) tt += Dh[r + k * NP] * gm[k + j * NX];
+				qp.A[r][j] = tt;
+			}
+			qp.A[r][NU] = h[r];
+			qp.b[r] = -s;
+			qp.eq[r] = false;
+		}
+		if (e.npKeep < NP) { // wave-uniform; npSSmax < npSS: rows beyond the npKeep smallest h are inert
+#pragma unroll
+			for (int r = 0; r < NP; r++) {
+				int p = 0;
+#pragma unroll
+				for (int q = 0; q < NP; q++) p += (h[q] < h[r] || (h[q] == h[r] && q < r)) ? 1 : 0;
+				const bool kept = p < e.npKeep;
+#pragma unroll
+				for (int j = 0; j < NV; j++) qp.A[r][j] = kept ? qp.A[r][j] : 0.0;
+				qp.b[r] = kept ? qp.b[r] : -1e20;
+			}
+		}
+#pragma unroll
+		for (int j = 0; j < NU; j++) {
+			qp.Hd[j] = 1.0;
+			qp.c[j] = -2.0 * uDes[j];
+			qp.lb[j] = el.lb[j];
+			qp.ub[j] = el.ub[j];
+		}
+		qp.Hd[NU] = el.relaxCost;
+		qp.c[NU] = -2.0 * el.relaxCost * el.relaxLb;
+		qp.lb[NU] = el.relaxLb;
+		qp.ub[NU] = el.relaxLb;
+		double sol[NV];
+		int iters;
+		const int verdict = GiSmall<NV, NC, 1>::template solve_with_pinned<NU>(qp, 0, 8 * NV + 4, sol, iters);
+		if constexpr (HASV) {
+#pragma unroll
+			for (int j = 0; j < NU; j++) arrived_p(vn[j]); // in front of this step's stores
+		}
+		if (live && a.xlog) {
+#pragma unroll
+			for (int k = 0; k < NX; k++) a.xlog[((int64_t)t * NX + k) * ld + i] = x[k];
+		}
+		const bool ok = (verdict == kGiOptimal) & gainOk;
+		if (ok) {
+#pragma unroll
+			for (int j = 0; j < NU; j++) uAct[j] = fmin(fmax(sol[j], el.lb[j]), el.ub[j]);
+			relax = sol[NU];
+		} else nfail++;
+		if (live && a.ulog) {
+#pragma unroll
+			for (int j = 0; j < NU; j++) a.ulog[((int64_t)t * NU + j) * ld + i] = uAct[j];
+		}
+		if (live && a.rclog) a.rclog[(int64_t)t * ld + i] = ok ? ASIF_HIP_RC_OK : ASIF_HIP_RC_QP_FAILED;
+		{
+#pragma clang fp contract(off)
+#pragma unroll
+			for (int k = 0; k < NX; k++) {
+				double fcl = 0.0;
+				fcl += f[k];
+#pragma unroll
+				for (int j = 0; j < NU; j++) fcl += uAct[j] * gm[k + j * NX];
+				x[k] += a.dt * fcl;
+			}
+		}
+#pragma unroll
+		for (int j = 0; j < NU; j++) v[j] = vn[j];
+	}
+	if (!live) return;
+#pragma unroll
+	for (int k = 0; k < NX; k++) a.x[k * ld + i] = x[k];
+#pragma unroll
+	for (int j = 0; j < NU; j++) a.uact[j * ld + i] = uAct[j];
+	a.relax[i] = relax;
+	a.nfail[i] = nfail;
+}
+
+template <class M>
+struct ParamStepLogs {
+	double x[M::NX], u[M::NU], gx[M::NX], gu[M::NU], v[M::NU];
+	int rc;
+};
+
+template <class M>
+__device__ __forceinline__ void load_param_step(const PolicyRolloutVjpArgs &a, int t, int64_t i, ParamStepLogs<M> &L)
+{
+	constexpr int NX = M::NX, NU = M::NU;
+#pragma unroll
+	for (int k = 0; k < NX; k++) {
+		const int64_t at = ((int64_t)t * NX + k) * a.ld + i;
+		L.x[k] = a.xlog[at];
+		L.gx[k] = a.gxlog ? a.gxlog[at] : 0.0; // wave-uniform
+	}
+#pragma unroll
+	for (int j = 0; j < NU; j++) {
+		const int64_t at = ((int64_t)t * NU + j) * a.ld + i;
+		L.u[j] = a.ulog[at];
+		L.gu[j] = a.gulog ? a.gulog[at] : 0.0;
+		L.v[j] = a.v ? a.v[at] : 0.0;
+	}
+	L.rc = a.rclog[(int64_t)t * a.ld + i];
+}
+
+template <class M, bool WANTP>
+__global__ __launch_bounds__(256) void rollout_params_vjp_kernel(RolloutVjpOpts<M::NU> e, ParamRolloutVjpArgs pa)
+{
+	static_assert(M::kIgnoresOptions, "the model's functors must not read DevOptions: only the class's fields are passed");
+	constexpr int NX = M::NX, NU = M::NU;
+	const PolicyRolloutVjpArgs &a = pa.p;
+	const DevOptions o = {};
+	int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const bool live = i < a.B;
+	if (!live) i = a.B - 1; // keep the lane in the wave votes of the solve; it never stores
+	const bool hasK = a.K != nullptr, hasV = a.v != nullptr; // wave-uniform
+	bool gainOk; // the forward pass's business: a step it failed is rc -1 in the log
+	const RolloutVjpOpts<NU> el = lane_opts<M>(e, pa.alpha, pa.lb, pa.ub, a.ld, i, gainOk);
+
+	double kk[NU], K[NU * NX];
+	ParamAdjoint<M> q;
+	PolicyAdjoint<M> &p = q.p;
+#pragma unroll
+	for (int k = 0; k < NX; k++) p.s.lam[k] = a.gxT[k * a.ld + i];
+#pragma unroll
+	for (int j = 0; j < NU; j++) {
+		kk[j] = a.k[j * a.ld + i];
+		p.s.mu[j] = a.guactT ? a.guactT[j * a.ld + i] : 0.0;
+		p.s.gudes[j] = 0.0;
+		p.gk[j] = 0.0;
+		q.glb[j] = 0.0;
+		q.gub[j] = 0.0;
+	}
+#pragma unroll
+	for (int c = 0; c < NU * NX; c++) {
+		K[c] = hasK ? a.K[c * a.ld + i] : 0.0;
+		p.gK[c] = 0.0;
+	}
+	p.s.nskip = 0;
+	q.galpha = 0.0;
+
+	ParamStepLogs<M> cur = {}, nxt = {};
+	if (a.T > 0) load_param_step<M>(a, a.T - 1, i, cur);
+#pragma unroll 1
+	for (int t = a.T - 1; t >= 0; t--) { // wave-uniform trip count
+		if (t > 0) load_param_step<M>(a, t - 1, i, nxt); // in flight behind this step's solve
+		rollout_params_vjp_step<M>(o, el, a.dt, cur.x, cur.u, kk, K, hasK, cur.v, hasV, cur.rc, cur.gx, cur.gu, WANTP, q);
+		if (live && a.gv) {
+#pragma unroll
+			for (int j = 0; j < NU; j++) a.gv[((int64_t)t * NU + j) * a.ld + i] = p.s.gudes[j];
+		}
+		cur = nxt;
+	}
+	if (!live) return;
+#pragma unroll
+	for (int k = 0; k < NX; k++) a.gx0[k * a.ld + i] = p.s.lam[k];
+#pragma unroll
+	for (int j = 0; j < NU; j++) {
+		a.gk[j * a.ld + i] = p.gk[j];
+		a.guact0[j * a.ld + i] = p.s.mu[j];
+		if (pa.glb) pa.glb[j * a.ld + i] = q.glb[j];
+		if (pa.gub) pa.gub[j * a.ld + i] = q.gub[j];
+	}
+	if (a.gK) {
+#pragma unroll
+		for (int c = 0; c < NU * NX; c++) a.gK[c * a.ld + i] = p.gK[c];
+	}
+	if (pa.galpha) pa.galpha[i] = q.galpha;
+	a.nskip[i] = p.s.nskip;
+}
+
+template <class M>
+static RolloutVjpOpts<M::NU> class_opts_p(const DevOptions &o)
+{
+	RolloutVjpOpts<M::NU> e;
+	for (int j = 0; j < M::NU; j++) {
+		e.lb[j] = o.lb[j];
+		e.ub[j] = o.ub[j];
+	}
+	e.relaxCost = o.relaxCost;
+	e.relaxLb = o.relaxLb;
+	e.npKeep = o.npKeep < M::NPSS ? o.npKeep : M::NPSS;
+	return e;
+}
+
+int launch_rollout_params_explicit_di(const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream)
+{
+	using M = DoubleIntegrator;
+	if (a.p.B <= 0 || a.p.T <= 0) return 0;
+	const dim3 grid(grid_for(a.p.B, 1, 256)), block(256);
+	if (a.p.v) hipLaunchKernelGGL((rollout_params_kernel<M, true>), grid, block, 0, stream, class_opts_p<M>(o), a);
+	else hipLaunchKernelGGL((rollout_params_kernel<M, false>), grid, block, 0, stream, class_opts_p<M>(o), a);
+	return (int)hipGetLastError();
+}
+
+// T == 0 runs the kernel too: the identity of launch_rollout_policy_vjp_explicit_di, and galpha = glb = gub = 0
+int launch_rollout_params_vjp_explicit_di(const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream)
+{
+	using M = DoubleIntegrator;
+	if (a.p.B <= 0) return 0;
+	const dim3 grid(grid_for(a.p.B, 1, 256)), block(256);
+	if (a.galpha || a.glb || a.gub)
+		hipLaunchKernelGGL((rollout_params_vjp_kernel<M, true>), grid, block, 0, stream, class_opts_p<M>(o), a);
+	else hipLaunchKernelGGL((rollout_params_vjp_kernel<M, false>), grid, block, 0, stream, class_opts_p<M>(o), a);
+	return (int)hipGetLastError();
+}
+
+} // namespace asif

@@ -108,6 +108,18 @@ struct PolicyRolloutVjpArgs {
 	int32_t *nskip;                      // [B]
 };
 int launch_rollout_policy_vjp_explicit_di(const DevOptions &o, const PolicyRolloutVjpArgs &a, hipStream_t stream);
+// the same rollout with the barrier gain and the input box per instance, and its adjoint (k_rollout_params.hip)
+struct ParamRolloutArgs {
+	PolicyRolloutArgs p;
+	const double *alpha, *lb, *ub; // [B], [nu][ld], [nu][ld]; each may be nullptr: the handle's value
+};
+int launch_rollout_params_explicit_di(const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream);
+struct ParamRolloutVjpArgs {
+	PolicyRolloutVjpArgs p;
+	const double *alpha, *lb, *ub; // as ParamRolloutArgs
+	double *galpha, *glb, *gub;    // [B], [nu][ld], [nu][ld]; each may be nullptr: not wanted
+};
+int launch_rollout_params_vjp_explicit_di(const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream);
 // plant Euler step x += dt (f(x) + g(x) uact) between two filter calls of the two-stage filters (k_rollout.hip);
 // logs the state / input / rc of the call just made (nullptr to skip) and counts rc < 0 into nfail
 int launch_plant_step(int model, const DevOptions &o, int64_t B, int64_t ld, double dt, double *x, const double *uact,

@@ -247,6 +247,100 @@ class PolicyRolloutLayer(torch.nn.Module):
         return PolicyRolloutFn.apply(self.filter, x0, k, K, v, uact_prev, self.T, self.dt)
 
 
+class ParamRolloutFn(torch.autograd.Function):
+    """xT, uactT, xlog, ulog, rclog, nfail = ParamRolloutFn.apply(flt, x0, k, K, v, uact_prev, alpha, lb, ub, T, dt)
+
+    PolicyRolloutFn with the filter's own parameters per instance: alpha [B], the barrier gain of
+    Lgh u + alpha h >= -Lfh (options.relaxLb), and the input box lb, ub [nu,B]; None is the handle's value.  Gradients
+    flow to x0, k, K, v, uact_prev, alpha, lb and ub.  Forward is one asif_hip_rollout_params_batch launch, backward one
+    asif_hip_rollout_params_vjp_batch launch; galpha / glb / gub are asked for only where the tensor requires a gradient.
+    A gain shared by the batch is alpha.expand(B) of a one-element parameter: autograd's own sum over the expanded axis
+    turns the per-instance galpha into the shared gain's gradient (likewise lb and ub through expand(-1, B))."""
+
+    @staticmethod
+    def forward(ctx, flt, x0, k, K, v, uact_prev, alpha, lb, ub, T, dt):
+        d = flt.dims
+        B = x0.shape[1]
+        T = int(T)
+        if T < 0:
+            raise ValueError(f"T: expected a non-negative step count, got {T}")
+        if flt.model != capi.MODEL_DOUBLE_INTEGRATOR or flt.variant != capi.EXPLICIT:
+            raise ValueError("the differentiable rollout exists for the explicit filter on the double integrator only")
+        x = _soa(x0, d.nx, B, "x0").clone()
+        k = _soa(k, d.nu, B, "k")
+        K = _soa(K, d.nu * d.nx, B, "K") if K is not None else None
+        if v is not None:
+            if v.dim() != 3 or v.shape[0] != T:
+                raise ValueError(f"v: expected shape ({T}, {d.nu}, {B}), got {tuple(v.shape)}")
+            v = _soa(v.reshape(T * d.nu, B), T * d.nu, B, "v").reshape(T, d.nu, B)
+        if alpha is not None:
+            if alpha.dim() != 1:
+                raise ValueError(f"alpha: expected shape ({B},), got {tuple(alpha.shape)}")
+            alpha = _soa(alpha[None, :], 1, B, "alpha")[0]
+        lb = _soa(lb, d.nu, B, "lb") if lb is not None else None
+        ub = _soa(ub, d.nu, B, "ub") if ub is not None else None
+        uact = (_soa(uact_prev, d.nu, B, "uact_prev").clone() if uact_prev is not None
+                else torch.zeros((d.nu, B), dtype=torch.float64, device=x.device))
+        relax = torch.zeros((d.nrelax, B), dtype=torch.float64, device=x.device)
+        nfail = torch.zeros(B, dtype=torch.int32, device=x.device)
+        xlog = torch.zeros((T, d.nx, B), dtype=torch.float64, device=x.device)
+        ulog = torch.zeros((T, d.nu, B), dtype=torch.float64, device=x.device)
+        rclog = torch.zeros((T, B), dtype=torch.int32, device=x.device)
+        if B > 0 and T > 0:
+            flt.rollout_params(T, float(dt), x, k, uact, relax, nfail, K=K, v=v, alpha=alpha, lb=lb, ub=ub, xlog=xlog,
+                               ulog=ulog, rclog=rclog)
+        opt = (K, v, alpha, lb, ub)
+        ctx.flt, ctx.T, ctx.dt, ctx.has = flt, T, float(dt), tuple(t is not None for t in opt)
+        ctx.save_for_backward(xlog, ulog, rclog, k, *(t for t in opt if t is not None))
+        ctx.mark_non_differentiable(rclog, nfail)
+        ctx.set_materialize_grads(False)
+        return x, uact, xlog, ulog, rclog, nfail
+
+    @staticmethod
+    def backward(ctx, gxT, guactT, gxlog, gulog, _grclog, _gnfail):
+        xlog, ulog, rclog, k = ctx.saved_tensors[:4]
+        rest = list(ctx.saved_tensors[4:])
+        K, v, alpha, lb, ub = (rest.pop(0) if has else None for has in ctx.has)
+        need = ctx.needs_input_grad[1:9]  # x0, k, K, v, uact_prev, alpha, lb, ub
+        given = [g for g in (gxT, guactT, gxlog, gulog) if g is not None]
+        if not any(need) or not given:  # nothing asked for, or no output was used: nothing to launch
+            return (None,) * 11
+        d = ctx.flt.dims
+        B, T = k.shape[1], ctx.T
+        cont = lambda g: None if g is None else g.contiguous()
+        gxT = cont(gxT) if gxT is not None else torch.zeros((d.nx, B), dtype=torch.float64, device=k.device)
+        gx0 = torch.empty((d.nx, B), dtype=torch.float64, device=k.device)
+        gk, guact0 = torch.empty_like(k), torch.empty_like(k)
+        gK = torch.empty_like(K) if K is not None and need[2] else None
+        gv = torch.empty_like(v) if v is not None and need[3] else None
+        galpha = torch.empty_like(alpha) if alpha is not None and need[5] else None
+        glb = torch.empty_like(lb) if lb is not None and need[6] else None
+        gub = torch.empty_like(ub) if ub is not None and need[7] else None
+        if B > 0:
+            steps = T > 0  # without a step there is no log, no v and no gv to hand over
+            ctx.flt.rollout_params_vjp(T, ctx.dt, xlog, ulog, rclog, k, gxT, gx0, gk, guact0,
+                                       torch.empty(B, dtype=torch.int32, device=k.device), K=K, v=v if steps else None,
+                                       alpha=alpha, lb=lb, ub=ub, guactT=cont(guactT),
+                                       gxlog=cont(gxlog) if steps else None, gulog=cont(gulog) if steps else None,
+                                       gK=gK, gv=gv if steps else None, galpha=galpha, glb=glb, gub=gub)
+        return (None, gx0 if need[0] else None, gk if need[1] else None, gK, gv, guact0 if need[4] else None, galpha,
+                glb, gub, None, None)
+
+
+class ParamRolloutLayer(torch.nn.Module):
+    """Owns an explicit capi.Filter and rolls the closed loop out for T steps of dt under udes_t = k + K x_t + v_t with
+    the barrier gain and the input box per instance:
+    xT, uactT, xlog, ulog, rclog, nfail = layer(x0, k, K=None, v=None, uact_prev=None, alpha=None, lb=None, ub=None)."""
+
+    def __init__(self, model=capi.MODEL_DOUBLE_INTEGRATOR, options=None, solver=None, device=0, T=1, dt=1e-3):
+        super().__init__()
+        self.filter = capi.Filter(model, capi.EXPLICIT, options=options, solver=solver, device=device)
+        self.T, self.dt = int(T), float(dt)
+
+    def forward(self, x0, k, K=None, v=None, uact_prev=None, alpha=None, lb=None, ub=None):
+        return ParamRolloutFn.apply(self.filter, x0, k, K, v, uact_prev, alpha, lb, ub, self.T, self.dt)
+
+
 class QPSolveFn(torch.autograd.Function):
     """sol, status = QPSolveFn.apply(Hd, c, A, b, lb, ub, be)
 

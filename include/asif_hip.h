@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define ASIF_HIP_VERSION 170 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
+#define ASIF_HIP_VERSION 180 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
                               * 120: ASIF_HIP_IMPLICIT_RB (options grew at the end), asif_hip_set_learning, asif_hip_affine_replay;
                               * 130: solver.adaptive_rho_interval (struct grew at the end), polish == 2 is the dual active-set
                               *      stage of gi_small.hpp;
@@ -59,7 +59,9 @@ extern "C" {
                               * 160: asif_hip_rollout_vjp_batch, the fused explicit rollout backwards (with the model's second
                               *      derivatives: a state gradient on the model's own Lie derivatives);
                               * 170: asif_hip_rollout_policy_batch / asif_hip_rollout_policy_vjp_batch, the fused explicit rollout
-                              *      and its adjoint under an affine policy uDes_t = k + K x_t + v_t evaluated inside the loop */
+                              *      and its adjoint under an affine policy uDes_t = k + K x_t + v_t evaluated inside the loop;
+                              * 180: asif_hip_rollout_params_batch / asif_hip_rollout_params_vjp_batch, that rollout and its adjoint
+                              *      with the barrier gain and the input box per instance, and their gradients */
 
 enum asif_hip_error {
 	ASIF_HIP_OK = 0,
@@ -407,6 +409,36 @@ int asif_hip_rollout_policy_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx,
                                       const double *v, const double *gxT, const double *guactT, const double *gxlog,
                                       const double *gulog, double *gx0, double *gK, double *gk, double *gv,
                                       double *guact0, int32_t *nskip, void *stream);
+
+/* asif_hip_rollout_policy_batch with the filter's own parameters per instance: three optional device arrays after v,
+ *   alpha[B]: the barrier gain, the alpha of Lgh u + alpha h >= -Lfh (options.relaxLb; the relaxation variable is pinned
+ *   to it, so relax returns alpha_i);  lb[nu][ldx], ub[nu][ldx]: the input box, also that of the final clamp.
+ * NULL means the handle's value for every instance; with all three NULL, and with arrays filled with the handle's own
+ * values, every output equals asif_hip_rollout_policy_batch's bit for bit.  relaxCost and npSSmax stay per handle.
+ * The arrays are data: a gain handed in that is not a positive finite number, lb_i > ub_i or a non-finite bound make every
+ * step of that instance fail (rclog -1, counted in nfail, u_t = u_{t-1}) and leave every other instance as it is.
+ * Everything else -- handles, refusals, B == 0, T == 0 -- as asif_hip_rollout_policy_batch. */
+int asif_hip_rollout_params_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, double *x,
+                                  const double *K, const double *k, const double *v, const double *alpha,
+                                  const double *lb, const double *ub, double *uact, double *relax, int32_t *nfail,
+                                  double *xlog, double *ulog, int32_t *rclog, void *stream);
+
+/* asif_hip_rollout_params_batch backwards, in one launch: asif_hip_rollout_policy_vjp_batch with each step's solve formed
+ * from the instance's parameters, and three optional outputs.  With W the constraint a solved step ends on and w its
+ * multiplier in the adjoint system (w = mu / normal):
+ *     galpha[B]      += -h_r w   W = safety row r;
+ *     glb[nu][ldx]   +=  w       W = the lower bound of input j;     gub[nu][ldx] += -w   W = its upper bound
+ * (both equal mu_j, the gradient arriving at u_t).  A failed or free step adds nothing; kinks on the forward pass's side.
+ *   alpha, lb, ub: as handed to the forward entry.  galpha without alpha, glb without lb, gub without ub: ASIF_HIP_EINVAL,
+ *   like gK without K.  T == 0: the identity, and galpha = glb = gub = 0.
+ * With the three parameters NULL every output equals asif_hip_rollout_policy_vjp_batch's bit for bit.  Everything else as
+ * that entry.  The handle's forward results do not change. */
+int asif_hip_rollout_params_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, const double *xlog,
+                                      const double *ulog, const int32_t *rclog, const double *K, const double *k,
+                                      const double *v, const double *alpha, const double *lb, const double *ub,
+                                      const double *gxT, const double *guactT, const double *gxlog, const double *gulog,
+                                      double *gx0, double *gK, double *gk, double *gv, double *galpha, double *glb,
+                                      double *gub, double *guact0, int32_t *nskip, void *stream);
 
 /* Rows only: A[(nc*nv)][ldx], b[nc][ldx], code[B] (1; TB: 2 trivial rows, -3 backup set unreached). */
 int asif_hip_assemble_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, double *A, double *b,
