@@ -1,23 +1,32 @@
 // k_rollout_policy.hip -- the fused explicit rollout (k_explicit.hip: explicit_rollout_kernel, light instantiation) with
-// the desired input coming from an affine policy evaluated inside the loop, and its adjoint:
-//     uDes_t = k + K x_t + v_t;   (ok_t, u*_t) = filter(x_t, uDes_t);   u_t = ok_t ? u*_t : u_{t-1};
+// the desired input coming from an affine policy evaluated inside the loop, optionally with the filter's own parameters
+// per instance, and its adjoint:
+//     uDes_t = k + K x_t + v_t;   (ok_t, u*_t) = filter(x_t, uDes_t; alpha_i, lb_i, ub_i);   u_t = ok_t ? u*_t : u_{t-1};
 //     x_{t+1} = x_t + dt (f(x_t) + g(x_t) u_t)
 // K (feedback gains, per instance) and v (a planned input sequence) are each optional; without both the forward kernel
 // computes what explicit_rollout_kernel<M, true> computes with udes = k, bit for bit, and the backward kernel what
 // rollout_vjp_kernel computes, with gk in the place of gudes.
+// Two uses, one source.  The policy entries (PARAMS = false) filter with the handle's options, which stay in scalar
+// registers.  The params entries (PARAMS = true) take alpha (the barrier gain: DevOptions::relaxLb), lb and ub per
+// instance, each optional: an absent one is the handle's value in every lane, and without all three they compute what the
+// policy entries compute, bit for bit.
 //
-// Forward: one instance per lane, 256-thread workgroups, x / uAct / K / k in registers for the whole rollout, the dual
-// active-set stage decides every step (no ADMM / finish code).  v_{t+1} depends on nothing step t computes: it is loaded
-// before step t's solve and waited for in front of step t's stores.  The row assembly and the plant step restate
-// explicit_rollout_kernel's.
-// Backward: rollout_vjp_kernel's structure around rollout_policy_step.hpp; lambda, mu, gk, gK in registers, the logs, their
-// gradients and v of step t-1 loaded behind step t's solve, gv[t] = d_t stored per step where the caller asked for it.
+// Forward: one instance per lane, 256-thread workgroups, x / uAct / K / k (and the three parameters) in registers for the
+// whole rollout, the dual active-set stage decides every step (no ADMM / finish code).  v_{t+1} depends on nothing step t
+// computes: it is loaded before step t's solve and waited for in front of step t's stores.  The step's QP is
+// explicit_step_qp (rollout_vjp_step.hpp); the plant step restates explicit_rollout_kernel's.
+// Backward: rollout_vjp_kernel's structure around rollout_params_step.hpp; lambda, mu, gk, gK (and galpha, glb, gub) in
+// registers, the logs, their gradients and v of step t-1 loaded behind step t's solve, gv[t] = d_t stored per step where
+// the caller asked for it.  WANTP (one of the three parameter gradients is asked for) is a template argument: without it
+// the step hands nothing out and the loop is the policy entry's.
 // HBM traffic per step and instance.  Forward: 8 nu read (v), 8 nx + 8 nu + 4 written (logs).  Backward: 8 nx + 8 nu + 4
-// of logs and 8 nu of v read, 8 (nx + nu) of log gradients where given, 8 nu written (gv) where asked for.
-// SoA, every load and store a coalesced line; no LDS, no scratch, no register array indexed by a run-time value.
+// of logs and 8 nu of v read, 8 (nx + nu) of log gradients where given, 8 nu written (gv) where asked for.  Per instance
+// and LAUNCH on top of that: 8 bytes read per parameter given, 8 written per parameter gradient asked for.
+// SoA, every load and store a coalesced line; no LDS, no scratch, no register array indexed by a run-time value.  Lanes
+// beyond B repeat instance B-1 for the solver's votes and never store.
 #include <cstdint>
 #include "launchers.hpp"
-#include "rollout_policy_step.hpp"
+#include "rollout_params_step.hpp"
 
 namespace asif {
 
@@ -27,13 +36,32 @@ namespace asif {
 // stores, the wait covers only operations issued a whole solve earlier.
 __device__ __forceinline__ void arrived(double &r) { asm volatile("" : "+v"(r)); }
 
+// the handle's fields, then the instance's own where given; gainOk: param_gain_usable of a gain that was handed in
+template <class M>
+__device__ __forceinline__ RolloutVjpOpts<M::NU> lane_opts(const RolloutVjpOpts<M::NU> &e, const double *alpha,
+                                                          const double *lb, const double *ub, int64_t ld, int64_t i,
+                                                          bool &gainOk)
+{
+	RolloutVjpOpts<M::NU> el = e;
+	if (alpha) el.relaxLb = alpha[i]; // wave-uniform, as the two below
+#pragma unroll
+	for (int j = 0; j < M::NU; j++) {
+		if (lb) el.lb[j] = lb[j * ld + i];
+		if (ub) el.ub[j] = ub[j * ld + i];
+	}
+	gainOk = alpha ? param_gain_usable(el.relaxLb) : true;
+	return el;
+}
+
 // HASV: v is given.  Without it the loop holds no load, as explicit_rollout_kernel's.
-template <class M, bool HASV>
-__global__ __launch_bounds__(256) void rollout_policy_kernel(RolloutVjpOpts<M::NU> e, PolicyRolloutArgs a)
+// PARAMS: pa.alpha, pa.lb, pa.ub are looked at.  Without it el is e and gainOk is true.
+template <class M, bool HASV, bool PARAMS>
+__global__ __launch_bounds__(256) void rollout_policy_kernel(RolloutVjpOpts<M::NU> e, ParamRolloutArgs pa)
 {
 	static_assert(M::kIgnoresOptions, "the model's functors must not read DevOptions: only the class's fields are passed");
 	static_assert(M::NU == 1, "one input: the pinned relaxation variable leaves a one-variable problem");
 	constexpr int NX = M::NX, NU = M::NU, NP = M::NPSS, NV = NU + 1, NC = NP;
+	const PolicyRolloutArgs &a = pa.p;
 	const DevOptions o = {};
 	int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	const bool live = i < a.B;
@@ -41,6 +69,9 @@ __global__ __launch_bounds__(256) void rollout_policy_kernel(RolloutVjpOpts<M::N
 	const int64_t ld = a.ld;
 	const bool hasK = a.K != nullptr; // wave-uniform
 	constexpr bool hasV = HASV;
+	bool gainOk = true;
+	RolloutVjpOpts<NU> el = e;
+	if constexpr (PARAMS) el = lane_opts<M>(e, pa.alpha, pa.lb, pa.ub, ld, i, gainOk);
 	double x[NX], uAct[NU], kk[NU], K[NU * NX], v[NU], vn[NU], relax;
 #pragma unroll
 	for (int k = 0; k < NX; k++) x[k] = a.x[k * ld + i];
@@ -59,10 +90,14 @@ __global__ __launch_bounds__(256) void rollout_policy_kernel(RolloutVjpOpts<M::N
 #pragma unroll
 		for (int k = 0; k < NX; k++) arrived(x[k]);
 #pragma unroll
-		for (int j = 0; j < NU; j++) arrived(kk[j]), arrived(uAct[j]), arrived(v[j]);
+		for (int j = 0; j < NU; j++) {
+			arrived(kk[j]), arrived(uAct[j]), arrived(v[j]);
+			if constexpr (PARAMS) arrived(el.lb[j]), arrived(el.ub[j]);
+		}
 #pragma unroll
 		for (int c = 0; c < NU * NX; c++) arrived(K[c]);
 		arrived(relax);
+		if constexpr (PARAMS) arrived(el.relaxLb);
 	}
 #pragma unroll 1
 	for (int t = 0; t < a.T; t++) { // wave-uniform trip count
@@ -76,45 +111,7 @@ __global__ __launch_bounds__(256) void rollout_policy_kernel(RolloutVjpOpts<M::N
 		M::safetySet(o, x, h, Dh);
 		M::dynamics(o, x, f, gm);
 		QpLaneData<NV, NC> qp;
-#pragma unroll
-		for (int r = 0; r < NP; r++) {
-			double s = 0.0;
-#pragma unroll
-			for (int k = 0; k < NX; k++) s += Dh[r + k * NP] * f[k];
-#pragma unroll
-			for (int j = 0; j < NU; j++) {
-				double tt = 0.0;
-#pragma unroll
-				for (int k = 0; k < NX; k++) tt += Dh[r + k * NP] * gm[k + j * NX];
-				qp.A[r][j] = tt;
-			}
-			qp.A[r][NU] = h[r];
-			qp.b[r] = -s;
-			qp.eq[r] = false;
-		}
-		if (e.npKeep < NP) { // wave-uniform; npSSmax < npSS: rows beyond the npKeep smallest h are inert
-#pragma unroll
-			for (int r = 0; r < NP; r++) {
-				int p = 0;
-#pragma unroll
-				for (int q = 0; q < NP; q++) p += (h[q] < h[r] || (h[q] == h[r] && q < r)) ? 1 : 0;
-				const bool kept = p < e.npKeep;
-#pragma unroll
-				for (int j = 0; j < NV; j++) qp.A[r][j] = kept ? qp.A[r][j] : 0.0;
-				qp.b[r] = kept ? qp.b[r] : -1e20;
-			}
-		}
-#pragma unroll
-		for (int j = 0; j < NU; j++) {
-			qp.Hd[j] = 1.0;
-			qp.c[j] = -2.0 * uDes[j];
-			qp.lb[j] = e.lb[j];
-			qp.ub[j] = e.ub[j];
-		}
-		qp.Hd[NU] = e.relaxCost;
-		qp.c[NU] = -2.0 * e.relaxCost * e.relaxLb;
-		qp.lb[NU] = e.relaxLb;
-		qp.ub[NU] = e.relaxLb;
+		explicit_step_qp<NX, NU, NP>(h, Dh, f, gm, uDes, el, qp);
 		double sol[NV];
 		int iters;
 		const int verdict = GiSmall<NV, NC, 1>::template solve_with_pinned<NU>(qp, 0, 8 * NV + 4, sol, iters);
@@ -126,12 +123,12 @@ __global__ __launch_bounds__(256) void rollout_policy_kernel(RolloutVjpOpts<M::N
 #pragma unroll
 			for (int k = 0; k < NX; k++) a.xlog[((int64_t)t * NX + k) * ld + i] = x[k];
 		}
-		const bool ok = verdict == kGiOptimal;
-		if (ok) {
+		const bool ok = (verdict == kGiOptimal) & gainOk;
+		// selects: written as `if (ok)`, whether the compiler if-converts the step's tail is left to its cost threshold
 #pragma unroll
-			for (int j = 0; j < NU; j++) uAct[j] = fmin(fmax(sol[j], e.lb[j]), e.ub[j]);
-			relax = sol[NU];
-		} else nfail++;
+		for (int j = 0; j < NU; j++) uAct[j] = ok ? fmin(fmax(sol[j], el.lb[j]), el.ub[j]) : uAct[j];
+		relax = ok ? sol[NU] : relax;
+		nfail += ok ? 0 : 1;
 		if (live && a.ulog) {
 #pragma unroll
 			for (int j = 0; j < NU; j++) a.ulog[((int64_t)t * NU + j) * ld + i] = uAct[j];
@@ -186,19 +183,26 @@ __device__ __forceinline__ void load_policy_step(const PolicyRolloutVjpArgs &a, 
 	L.rc = a.rclog[(int64_t)t * a.ld + i];
 }
 
-template <class M>
-__global__ __launch_bounds__(256) void rollout_policy_vjp_kernel(RolloutVjpOpts<M::NU> e, PolicyRolloutVjpArgs a)
+// PARAMS: as the forward kernel's.  WANTP: one of pa.galpha, pa.glb, pa.gub is given (PARAMS only).
+template <class M, bool PARAMS, bool WANTP>
+__global__ __launch_bounds__(256) void rollout_policy_vjp_kernel(RolloutVjpOpts<M::NU> e, ParamRolloutVjpArgs pa)
 {
 	static_assert(M::kIgnoresOptions, "the model's functors must not read DevOptions: only the class's fields are passed");
+	static_assert(PARAMS || !WANTP, "a parameter gradient belongs to a parameter");
 	constexpr int NX = M::NX, NU = M::NU;
+	const PolicyRolloutVjpArgs &a = pa.p;
 	const DevOptions o = {};
 	int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	const bool live = i < a.B;
 	if (!live) i = a.B - 1; // keep the lane in the wave votes of the solve; it never stores
 	const bool hasK = a.K != nullptr, hasV = a.v != nullptr; // wave-uniform
+	bool gainOk; // the forward pass's business: a step it failed is rc -1 in the log
+	RolloutVjpOpts<NU> el = e;
+	if constexpr (PARAMS) el = lane_opts<M>(e, pa.alpha, pa.lb, pa.ub, a.ld, i, gainOk);
 
 	double kk[NU], K[NU * NX];
-	PolicyAdjoint<M> p;
+	ParamAdjoint<M> q;
+	PolicyAdjoint<M> &p = q.p;
 #pragma unroll
 	for (int k = 0; k < NX; k++) p.s.lam[k] = a.gxT[k * a.ld + i];
 #pragma unroll
@@ -207,6 +211,8 @@ __global__ __launch_bounds__(256) void rollout_policy_vjp_kernel(RolloutVjpOpts<
 		p.s.mu[j] = a.guactT ? a.guactT[j * a.ld + i] : 0.0;
 		p.s.gudes[j] = 0.0;
 		p.gk[j] = 0.0;
+		q.glb[j] = 0.0;
+		q.gub[j] = 0.0;
 	}
 #pragma unroll
 	for (int c = 0; c < NU * NX; c++) {
@@ -214,13 +220,14 @@ __global__ __launch_bounds__(256) void rollout_policy_vjp_kernel(RolloutVjpOpts<
 		p.gK[c] = 0.0;
 	}
 	p.s.nskip = 0;
+	q.galpha = 0.0;
 
 	PolicyStepLogs<M> cur = {}, nxt = {};
 	if (a.T > 0) load_policy_step<M>(a, a.T - 1, i, cur);
 #pragma unroll 1
 	for (int t = a.T - 1; t >= 0; t--) { // wave-uniform trip count
 		if (t > 0) load_policy_step<M>(a, t - 1, i, nxt); // in flight behind this step's solve
-		rollout_policy_vjp_step<M>(o, e, a.dt, cur.x, cur.u, kk, K, hasK, cur.v, hasV, cur.rc, cur.gx, cur.gu, p);
+		rollout_params_vjp_step<M>(o, el, a.dt, cur.x, cur.u, kk, K, hasK, cur.v, hasV, cur.rc, cur.gx, cur.gu, WANTP, q);
 		if (live && a.gv) {
 #pragma unroll
 			for (int j = 0; j < NU; j++) a.gv[((int64_t)t * NU + j) * a.ld + i] = p.s.gudes[j];
@@ -234,46 +241,66 @@ __global__ __launch_bounds__(256) void rollout_policy_vjp_kernel(RolloutVjpOpts<
 	for (int j = 0; j < NU; j++) {
 		a.gk[j * a.ld + i] = p.gk[j];
 		a.guact0[j * a.ld + i] = p.s.mu[j];
+		if constexpr (PARAMS) {
+			if (pa.glb) pa.glb[j * a.ld + i] = q.glb[j];
+			if (pa.gub) pa.gub[j * a.ld + i] = q.gub[j];
+		}
 	}
 	if (a.gK) {
 #pragma unroll
 		for (int c = 0; c < NU * NX; c++) a.gK[c * a.ld + i] = p.gK[c];
 	}
+	if constexpr (PARAMS) {
+		if (pa.galpha) pa.galpha[i] = q.galpha;
+	}
 	a.nskip[i] = p.s.nskip;
 }
 
-template <class M>
-static RolloutVjpOpts<M::NU> class_opts(const DevOptions &o)
+template <bool PARAMS>
+static int launch_forward(const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream)
 {
-	RolloutVjpOpts<M::NU> e;
-	for (int j = 0; j < M::NU; j++) {
-		e.lb[j] = o.lb[j];
-		e.ub[j] = o.ub[j];
-	}
-	e.relaxCost = o.relaxCost;
-	e.relaxLb = o.relaxLb;
-	e.npKeep = o.npKeep < M::NPSS ? o.npKeep : M::NPSS;
-	return e;
+	using M = DoubleIntegrator;
+	if (a.p.B <= 0 || a.p.T <= 0) return 0;
+	const dim3 grid(grid_for(a.p.B, 1, 256)), block(256);
+	const RolloutVjpOpts<M::NU> e = rollout_class_opts<M>(o);
+	if (a.p.v) hipLaunchKernelGGL((rollout_policy_kernel<M, true, PARAMS>), grid, block, 0, stream, e, a);
+	else hipLaunchKernelGGL((rollout_policy_kernel<M, false, PARAMS>), grid, block, 0, stream, e, a);
+	return (int)hipGetLastError();
+}
+
+template <bool PARAMS, bool WANTP>
+static int launch_backward(const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream)
+{
+	using M = DoubleIntegrator;
+	if (a.p.B <= 0) return 0;
+	hipLaunchKernelGGL((rollout_policy_vjp_kernel<M, PARAMS, WANTP>), dim3(grid_for(a.p.B, 1, 256)), dim3(256), 0, stream,
+	                   rollout_class_opts<M>(o), a);
+	return (int)hipGetLastError();
 }
 
 int launch_rollout_policy_explicit_di(const DevOptions &o, const PolicyRolloutArgs &a, hipStream_t stream)
 {
-	using M = DoubleIntegrator;
-	if (a.B <= 0 || a.T <= 0) return 0;
-	const dim3 grid(grid_for(a.B, 1, 256)), block(256);
-	if (a.v) hipLaunchKernelGGL((rollout_policy_kernel<M, true>), grid, block, 0, stream, class_opts<M>(o), a);
-	else hipLaunchKernelGGL((rollout_policy_kernel<M, false>), grid, block, 0, stream, class_opts<M>(o), a);
-	return (int)hipGetLastError();
+	return launch_forward<false>(o, ParamRolloutArgs{a, nullptr, nullptr, nullptr}, stream);
 }
 
 // T == 0 runs the kernel too: it writes the identity (gx0 = gxT, guact0 = guactT or 0, gk = 0, gK = 0, nskip = 0, no gv)
 int launch_rollout_policy_vjp_explicit_di(const DevOptions &o, const PolicyRolloutVjpArgs &a, hipStream_t stream)
 {
-	using M = DoubleIntegrator;
-	if (a.B <= 0) return 0;
-	hipLaunchKernelGGL((rollout_policy_vjp_kernel<M>), dim3(grid_for(a.B, 1, 256)), dim3(256), 0, stream, class_opts<M>(o),
-	                   a);
-	return (int)hipGetLastError();
+	return launch_backward<false, false>(
+		o, ParamRolloutVjpArgs{a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, stream);
+}
+
+// the PARAMS kernels also where all three parameters are absent
+int launch_rollout_params_explicit_di(const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream)
+{
+	return launch_forward<true>(o, a, stream);
+}
+
+// T == 0: the identity of launch_rollout_policy_vjp_explicit_di, and galpha = glb = gub = 0
+int launch_rollout_params_vjp_explicit_di(const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream)
+{
+	if (a.galpha || a.glb || a.gub) return launch_backward<true, true>(o, a, stream);
+	return launch_backward<true, false>(o, a, stream);
 }
 
 } // namespace asif

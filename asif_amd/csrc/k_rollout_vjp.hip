@@ -86,15 +86,8 @@ int launch_rollout_vjp_explicit_di(const DevOptions &o, const RolloutVjpArgs &a,
 	using M = DoubleIntegrator;
 	if (a.B <= 0) return 0;
 	const int block = 256;
-	RolloutVjpOpts<M::NU> e;
-	for (int j = 0; j < M::NU; j++) {
-		e.lb[j] = o.lb[j];
-		e.ub[j] = o.ub[j];
-	}
-	e.relaxCost = o.relaxCost;
-	e.relaxLb = o.relaxLb;
-	e.npKeep = o.npKeep < M::NPSS ? o.npKeep : M::NPSS;
-	hipLaunchKernelGGL((rollout_vjp_kernel<M>), dim3(grid_for(a.B, 1, block)), dim3(block), 0, stream, e, a);
+	hipLaunchKernelGGL((rollout_vjp_kernel<M>), dim3(grid_for(a.B, 1, block)), dim3(block), 0, stream,
+	                   rollout_class_opts<M>(o), a);
 	return (int)hipGetLastError();
 }
 

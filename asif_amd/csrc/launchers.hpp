@@ -108,7 +108,7 @@ struct PolicyRolloutVjpArgs {
 	int32_t *nskip;                      // [B]
 };
 int launch_rollout_policy_vjp_explicit_di(const DevOptions &o, const PolicyRolloutVjpArgs &a, hipStream_t stream);
-// the same rollout with the barrier gain and the input box per instance, and its adjoint (k_rollout_params.hip)
+// the same rollout with the barrier gain and the input box per instance, and its adjoint (k_rollout_policy.hip, PARAMS)
 struct ParamRolloutArgs {
 	PolicyRolloutArgs p;
 	const double *alpha, *lb, *ub; // [B], [nu][ld], [nu][ld]; each may be nullptr: the handle's value

@@ -12,7 +12,7 @@
 // Backward step: rollout_vjp_step.hpp unchanged, called with its gudes zeroed, so that what it leaves there is the
 // step's own d_t = dL/duDes_t (mu on a free step; zero on a failed step and on one that ends on a row or a bound), and
 //     gk += d_t;   gK[j,m] += d_t[j] x_t[m];   gv[t] = d_t (the caller's store);   lambda += K' d_t
-// where lambda is the value the step leaves for t-1: x_t reaches uDes_t through K.
+// where lambda is the value the step leaves for t-1: x_t reaches uDes_t through K.  out is the wrapped step's, passed on.
 //
 // Compiles for the host like the file it wraps (tests/host_rollout_policy_driver.cpp).
 #pragma once
@@ -49,14 +49,15 @@ template <class M, class O>
 ASIF_HD void rollout_policy_vjp_step(const O &o, const RolloutVjpOpts<M::NU> &e, double dt, const double (&x)[M::NX],
                                      const double (&ut)[M::NU], const double (&k)[M::NU],
                                      const double (&K)[M::NU * M::NX], bool hasK, const double (&v)[M::NU], bool hasV,
-                                     int rc, const double (&gxl)[M::NX], const double (&gul)[M::NU], PolicyAdjoint<M> &p)
+                                     int rc, const double (&gxl)[M::NX], const double (&gul)[M::NU], PolicyAdjoint<M> &p,
+                                     StepWorkingSet<M> *out = nullptr)
 {
 	constexpr int NX = M::NX, NU = M::NU;
 	double uDes[NU];
 	policy_udes<NX, NU>(k, K, hasK, x, v, hasV, uDes);
 #pragma unroll
 	for (int j = 0; j < NU; j++) p.s.gudes[j] = 0.0;
-	rollout_vjp_step<M>(o, e, dt, x, ut, uDes, rc, gxl, gul, p.s);
+	rollout_vjp_step<M>(o, e, dt, x, ut, uDes, rc, gxl, gul, p.s, out);
 #pragma unroll
 	for (int j = 0; j < NU; j++) p.gk[j] += p.s.gudes[j];
 	if (hasK) {

@@ -18,6 +18,9 @@
 // Kinks are taken on the side the forward pass took: the branch of the model's safety set, the row order under
 // npSSmax, a constraint met with equality but outside W, the clamp.
 //
+// out, where given, receives the step's verdict, W, w and h: the filter's parameters enter the QP only through the rows'
+// h column and the box, so their gradients are sums over these (rollout_params_step.hpp) and need no solve of their own.
+//
 // rc is the caller's record of what the forward pass decided.  rc == 1 next to a solve of this file that does not end
 // optimal (not possible on the same code and the same bits) contributes nothing: mu = 0 and the step is counted.
 //
@@ -35,16 +38,90 @@ struct RolloutVjpOpts { // the fields of DevOptions the explicit class reads (se
 	int npKeep;
 };
 
+// o: DevOptions (a template argument only because this file compiles for the host without models.hpp)
+template <class M, class DO>
+inline RolloutVjpOpts<M::NU> rollout_class_opts(const DO &o)
+{
+	RolloutVjpOpts<M::NU> e;
+	for (int j = 0; j < M::NU; j++) {
+		e.lb[j] = o.lb[j];
+		e.ub[j] = o.ub[j];
+	}
+	e.relaxCost = o.relaxCost;
+	e.relaxLb = o.relaxLb;
+	e.npKeep = o.npKeep < M::NPSS ? o.npKeep : M::NPSS;
+	return e;
+}
+
+// The QP of the explicit class at one state, from the model's h, Dh, f, g there: the one statement of it for the fused
+// rollouts under a policy and for every adjoint step (explicit_rollout_kernel in k_explicit.hip keeps a copy of its own).
+//     min |u - uDes|^2 + relaxCost (d - relaxLb)^2   s.t.  Lgh_r u + h_r d >= -Lfh_r,  lb <= u <= ub,  d = relaxLb
+// with Lfh = Dh f, Lgh = Dh g and the relaxation variable d, the last one, pinned by its bounds.  npKeep < NP (npSSmax <
+// npSS): only the rows of the npKeep smallest h count, ties going to the lower index; the others are zero with
+// b = -1e20, inert.
+template <int NX, int NU, int NP>
+ASIF_HD void explicit_step_qp(const double (&h)[NP], const double (&Dh)[NP * NX], const double (&f)[NX],
+                              const double (&gm)[NX * NU], const double (&uDes)[NU], const RolloutVjpOpts<NU> &e,
+                              QpLaneData<NU + 1, NP> &qp)
+{
+#pragma unroll
+	for (int r = 0; r < NP; r++) {
+		double s = 0.0;
+#pragma unroll
+		for (int k = 0; k < NX; k++) s += Dh[r + k * NP] * f[k];
+#pragma unroll
+		for (int j = 0; j < NU; j++) {
+			double t = 0.0;
+#pragma unroll
+			for (int k = 0; k < NX; k++) t += Dh[r + k * NP] * gm[k + j * NX];
+			qp.A[r][j] = t;
+		}
+		qp.A[r][NU] = h[r];
+		qp.b[r] = -s;
+		qp.eq[r] = false;
+	}
+	if (e.npKeep < NP) { // the same for every instance of a launch
+#pragma unroll
+		for (int r = 0; r < NP; r++) {
+			int p = 0;
+#pragma unroll
+			for (int q = 0; q < NP; q++) p += (h[q] < h[r] || (h[q] == h[r] && q < r)) ? 1 : 0;
+			const bool kept = p < e.npKeep;
+#pragma unroll
+			for (int j = 0; j < NU + 1; j++) qp.A[r][j] = kept ? qp.A[r][j] : 0.0;
+			qp.b[r] = kept ? qp.b[r] : -1e20;
+		}
+	}
+#pragma unroll
+	for (int j = 0; j < NU; j++) {
+		qp.Hd[j] = 1.0;
+		qp.c[j] = -2.0 * uDes[j];
+		qp.lb[j] = e.lb[j];
+		qp.ub[j] = e.ub[j];
+	}
+	qp.Hd[NU] = e.relaxCost;
+	qp.c[NU] = -2.0 * e.relaxCost * e.relaxLb;
+	qp.lb[NU] = e.relaxLb;
+	qp.ub[NU] = e.relaxLb;
+}
+
 template <class M>
 struct RolloutAdjoint { // what the sweep carries from step to step
 	double lam[M::NX], mu[M::NU], gudes[M::NU];
 	int nskip;
 };
 
+template <class M>
+struct StepWorkingSet { // what a step knows of its filter call, for a caller that differentiates the filter's parameters
+	bool use;           // rc == 1 and the repeated solve ended optimal
+	int id[M::NU];      // W, ids as GiWorkingSet's
+	double w[M::NU], h[M::NPSS]; // the multiplier of the adjoint system per slot of W; the safety functions at x
+};
+
 template <class M, class O>
 ASIF_HD void rollout_vjp_step(const O &o, const RolloutVjpOpts<M::NU> &e, double dt, const double (&x)[M::NX],
                               const double (&ut)[M::NU], const double (&uDes)[M::NU], int rc, const double (&gxl)[M::NX],
-                              const double (&gul)[M::NU], RolloutAdjoint<M> &s)
+                              const double (&gul)[M::NU], RolloutAdjoint<M> &s, StepWorkingSet<M> *out = nullptr)
 {
 	constexpr int NX = M::NX, NU = M::NU, NP = M::NPSS, NV = NU + 1, NC = NP;
 	static_assert(NU == 1 || NU == 2, "closed-form adjoint: 1 x 1 or 2 x 2");
@@ -76,56 +153,9 @@ ASIF_HD void rollout_vjp_step(const O &o, const RolloutVjpOpts<M::NU> &e, double
 		lamn[m] = s.lam[m] + dt * t + gxl[m];
 	}
 
-	// ---- 2. the rows, as explicit_rollout_kernel assembles them
-	double Lfh[NP], Lgh[NP * NU];
-#pragma unroll
-	for (int r = 0; r < NP; r++) {
-		double a = 0.0;
-#pragma unroll
-		for (int k = 0; k < NX; k++) a += Dh[r + k * NP] * f[k];
-		Lfh[r] = a;
-#pragma unroll
-		for (int j = 0; j < NU; j++) {
-			double t = 0.0;
-#pragma unroll
-			for (int k = 0; k < NX; k++) t += Dh[r + k * NP] * gm[k + j * NX];
-			Lgh[r + j * NP] = t;
-		}
-	}
-	// npSSmax < npSS: the rows of the nkeep smallest h (ties: lower index first); the others are inert
-	const int nkeep = e.npKeep;
-	bool kept[NP];
-#pragma unroll
-	for (int r = 0; r < NP; r++) kept[r] = true;
-	if (nkeep < NP) { // the same for every instance of a launch
-#pragma unroll
-		for (int r = 0; r < NP; r++) {
-			int p = 0;
-#pragma unroll
-			for (int q = 0; q < NP; q++) p += (h[q] < h[r] || (h[q] == h[r] && q < r)) ? 1 : 0;
-			kept[r] = p < nkeep;
-		}
-	}
+	// ---- 2. the step's QP
 	QpLaneData<NV, NC> qp;
-#pragma unroll
-	for (int j = 0; j < NU; j++) {
-		qp.Hd[j] = 1.0;
-		qp.c[j] = -2.0 * uDes[j];
-		qp.lb[j] = e.lb[j];
-		qp.ub[j] = e.ub[j];
-	}
-	qp.Hd[NU] = e.relaxCost;
-	qp.c[NU] = -2.0 * e.relaxCost * e.relaxLb;
-	qp.lb[NU] = e.relaxLb;
-	qp.ub[NU] = e.relaxLb;
-#pragma unroll
-	for (int r = 0; r < NC; r++) {
-#pragma unroll
-		for (int j = 0; j < NU; j++) qp.A[r][j] = kept[r] ? Lgh[r + j * NP] : 0.0;
-		qp.A[r][NU] = kept[r] ? h[r] : 0.0;
-		qp.b[r] = kept[r] ? -Lfh[r] : -1e20;
-		qp.eq[r] = false;
-	}
+	explicit_step_qp<NX, NU, NP>(h, Dh, f, gm, uDes, e, qp);
 
 	// ---- 3. the forward solve, and the working set it ends with
 	double sol[NV];
@@ -155,6 +185,13 @@ ASIF_HD void rollout_vjp_step(const O &o, const RolloutVjpOpts<M::NU> &e, double
 		w[1] = both ? (n0[0] * s.mu[1] - s.mu[0] * n0[1]) * idet : ((one & v1) ? w1d : 0.0);
 #pragma unroll
 		for (int j = 0; j < 2; j++) z[j] = both ? 0.0 : 0.5 * (s.mu[j] - w[0] * n0[j] - w[1] * n1[j]);
+	}
+	if (out) { // known where the call is inlined: a caller that passes nothing pays nothing
+		out->use = use;
+#pragma unroll
+		for (int t = 0; t < NU; t++) out->id[t] = ws.id[t], out->w[t] = w[t];
+#pragma unroll
+		for (int r = 0; r < NP; r++) out->h[r] = h[r];
 	}
 	// per safety function: the gradient of its row (zero outside W), then its share of dL/dx_t through h, Lfh and Lgh
 	double add[NX];

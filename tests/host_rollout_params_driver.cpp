@@ -1,8 +1,8 @@
 // host_rollout_params_driver.cpp -- TEST HARNESS: the per-step adjoint of the fused explicit rollout with the barrier gain
 // and the input box per instance (asif_amd/csrc/rollout_params_step.hpp, one lane per instance) compiled with g++ and
 // exposed through a C entry, so that tests/test_rollout_params_ref_host.py can compare it with the numpy sweep of
-// tests/rollout_params_ref.py on the CPU.  It walks the batch and the steps the way rollout_params_vjp_kernel
-// (k_rollout_params.hip) does.  models.hpp is device code; the double integrator's functors
+// tests/rollout_params_ref.py on the CPU.  It walks the batch and the steps the way rollout_policy_vjp_kernel with PARAMS
+// (k_rollout_policy.hip) does.  models.hpp is device code; the double integrator's functors
 // (examples/DoubleIntegrator.cpp:12-61 and their derivatives) are restated here in plain C++, as in
 // host_rollout_policy_driver.cpp.  Not part of any library the product ships.
 // With -DPARAMS_DRIVER_MAIN the file is a stand-alone program (for a sanitizer build of the host code): it runs a small

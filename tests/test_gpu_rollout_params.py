@@ -1,4 +1,4 @@
-"""asif_hip_rollout_params_batch / asif_hip_rollout_params_vjp_batch (asif_amd/csrc/k_rollout_params.hip) and the torch
+"""asif_hip_rollout_params_batch / asif_hip_rollout_params_vjp_batch (asif_amd/csrc/k_rollout_policy.hip, PARAMS) and the torch
 layer on top of them: the fused explicit rollout under an affine policy with the barrier gain alpha_i and the input box
 lb_i, ub_i per instance.
 
