@@ -37,6 +37,8 @@ IMPLICIT_RB = 5
 MODEL_INVERTED_PENDULUM_TB = 6
 MODEL_DOUBLE_INTEGRATOR_IMPLICIT = 7
 MODEL_DOUBLE_INTEGRATOR_TB = 9
+# not a reference example: the synthetic cart-driven pendulum, class ASIF's nonlinear one-input model (explicit only)
+MODEL_CART_PENDULUM = 10
 
 EXPORTS = [
     "asif_hip_version", "asif_hip_error_string", "asif_hip_device_count", "asif_hip_default_options",

@@ -107,6 +107,10 @@ extern "C" int asif_hip_default_options(int model, int variant, asif_hip_options
 		o->lb[0] = o->lb[1] = -1.0;
 		o->ub[0] = o->ub[1] = 1.0;
 		break;
+	case ASIF_HIP_MODEL_CART_PENDULUM: // synthetic (a nonlinear plant for the differentiable rollouts): class defaults
+		o->lb[0] = -4.0;
+		o->ub[0] = 4.0;
+		break;
 	case ASIF_HIP_MODEL_INVERTED_PENDULUM:
 		o->lb[0] = -1.5;
 		o->ub[0] = 1.5;
@@ -259,8 +263,8 @@ static int model_dims(int model, int variant, const asif_hip_options &o, asif_hi
 	dev.integrator = o.integrator;
 	dev.trajAbsTol = o.backTrajAbsTol;
 	dev.trajRelTol = o.backTrajRelTol;
-	if ((model == ASIF_HIP_MODEL_DOUBLE_INTEGRATOR || model == ASIF_HIP_MODEL_PLANAR_TWO_INPUT) &&
-	    variant == ASIF_HIP_EXPLICIT) {
+	if ((model == ASIF_HIP_MODEL_DOUBLE_INTEGRATOR || model == ASIF_HIP_MODEL_PLANAR_TWO_INPUT ||
+	     model == ASIF_HIP_MODEL_CART_PENDULUM) && variant == ASIF_HIP_EXPLICIT) {
 		const bool p2 = model == ASIF_HIP_MODEL_PLANAR_TWO_INPUT;
 		d.nx = 2; d.nu = p2 ? 2 : 1; d.npSS = p2 ? 5 : 4;
 		d.nv = d.nu + 1;  // src/asif.cpp:19
@@ -900,6 +904,8 @@ static int run_filter(asif_hip_ctx *ctx, FilterArgs a, bool assemble_only, hipSt
 		return launch_explicit_di(ctx->dev, ctx->solver, a, assemble_only, stream);
 	if (ctx->model == ASIF_HIP_MODEL_PLANAR_TWO_INPUT && ctx->variant == ASIF_HIP_EXPLICIT)
 		return launch_explicit_p2(ctx->dev, ctx->solver, a, assemble_only, stream);
+	if (ctx->model == ASIF_HIP_MODEL_CART_PENDULUM && ctx->variant == ASIF_HIP_EXPLICIT)
+		return launch_explicit_cp(ctx->dev, ctx->solver, a, assemble_only, stream);
 	// ASIFimplicitRB, and ASIFimplicit with its learned residual switched on (src/asif_implicit.cpp:585-588):
 	// the latter runs the RB rows kernel with the hold off (backContDt = 0) and zero uncertainty, which is
 	// bitwise the plain kernel plus the residual
@@ -1009,6 +1015,7 @@ extern "C" int asif_hip_filter_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t l
 	const VjpArgs a = {B, ldx, x, udes, lfh, lgh, guact, gudes, glfh, glgh, gx, rc};
 	if (ctx->model == ASIF_HIP_MODEL_DOUBLE_INTEGRATOR) return launch_explicit_vjp_di(ctx->dev, a, (hipStream_t)stream);
 	if (ctx->model == ASIF_HIP_MODEL_PLANAR_TWO_INPUT) return launch_explicit_vjp_p2(ctx->dev, a, (hipStream_t)stream);
+	if (ctx->model == ASIF_HIP_MODEL_CART_PENDULUM) return launch_explicit_vjp_cp(ctx->dev, a, (hipStream_t)stream);
 	return ASIF_HIP_EUNSUPPORTED;
 }
 
@@ -1074,11 +1081,12 @@ extern "C" int asif_hip_rollout_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t 
 	return launch_rollout_vjp_explicit_di(ctx->dev, a, (hipStream_t)stream);
 }
 
-// both policy entries: the fused path's handle, in the solver mode the light kernel implements
+// the four policy / params entries: the fused path's handle (the double integrator or the cart-driven pendulum), in the
+// solver mode the light kernel implements
 static int policy_rollout_handle(const asif_hip_ctx *ctx, bool presolve_too)
 {
-	if (ctx->variant != ASIF_HIP_EXPLICIT || ctx->rz || ctx->rb || ctx->model != ASIF_HIP_MODEL_DOUBLE_INTEGRATOR)
-		return ASIF_HIP_EUNSUPPORTED;
+	const bool model = ctx->model == ASIF_HIP_MODEL_DOUBLE_INTEGRATOR || ctx->model == ASIF_HIP_MODEL_CART_PENDULUM;
+	if (ctx->variant != ASIF_HIP_EXPLICIT || ctx->rz || ctx->rb || !model) return ASIF_HIP_EUNSUPPORTED;
 	const asif_hip_solver &S = ctx->solver;
 	const bool light = S.polish == 2 || (presolve_too && S.presolve); // launch_rollout_explicit_di's choice
 	if (!light || (S.lanes_per_qp != 0 && S.lanes_per_qp != 1)) return ASIF_HIP_EUNSUPPORTED;
@@ -1096,7 +1104,7 @@ extern "C" int asif_hip_rollout_policy_batch(asif_hip_ctx *ctx, int64_t B, int64
 	hipError_t e = hipSetDevice(ctx->device);
 	if (e != hipSuccess) return (int)e;
 	const PolicyRolloutArgs a = {B, ldx, T, dt, x, K, k, v, uact, relax, nfail, xlog, ulog, rclog};
-	return launch_rollout_policy_explicit_di(ctx->dev, a, (hipStream_t)stream);
+	return launch_rollout_policy_explicit(ctx->model, ctx->dev, a, (hipStream_t)stream);
 }
 
 extern "C" int asif_hip_rollout_policy_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt,
@@ -1116,7 +1124,7 @@ extern "C" int asif_hip_rollout_policy_vjp_batch(asif_hip_ctx *ctx, int64_t B, i
 	if (e != hipSuccess) return (int)e;
 	const PolicyRolloutVjpArgs a = {B,   ldx,    T,     dt,    xlog, ulog, rclog, K,  k,      v,
 	                                gxT, guactT, gxlog, gulog, gx0,  gK,   gk,    gv, guact0, nskip};
-	return launch_rollout_policy_vjp_explicit_di(ctx->dev, a, (hipStream_t)stream);
+	return launch_rollout_policy_vjp_explicit(ctx->model, ctx->dev, a, (hipStream_t)stream);
 }
 
 extern "C" int asif_hip_rollout_params_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, double *x,
@@ -1130,7 +1138,7 @@ extern "C" int asif_hip_rollout_params_batch(asif_hip_ctx *ctx, int64_t B, int64
 	hipError_t e = hipSetDevice(ctx->device);
 	if (e != hipSuccess) return (int)e;
 	const ParamRolloutArgs a = {{B, ldx, T, dt, x, K, k, v, uact, relax, nfail, xlog, ulog, rclog}, alpha, lb, ub};
-	return launch_rollout_params_explicit_di(ctx->dev, a, (hipStream_t)stream);
+	return launch_rollout_params_explicit(ctx->model, ctx->dev, a, (hipStream_t)stream);
 }
 
 extern "C" int asif_hip_rollout_params_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt,
@@ -1153,7 +1161,7 @@ extern "C" int asif_hip_rollout_params_vjp_batch(asif_hip_ctx *ctx, int64_t B, i
 	const ParamRolloutVjpArgs a = {{B,   ldx,    T,     dt,    xlog, ulog, rclog, K,  k,      v,
 	                                gxT, guactT, gxlog, gulog, gx0,  gK,   gk,    gv, guact0, nskip},
 	                               alpha, lb, ub, galpha, glb, gub};
-	return launch_rollout_params_vjp_explicit_di(ctx->dev, a, (hipStream_t)stream);
+	return launch_rollout_params_vjp_explicit(ctx->model, ctx->dev, a, (hipStream_t)stream);
 }
 
 extern "C" int asif_hip_assemble_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, double *A,

@@ -213,5 +213,9 @@ int launch_explicit_vjp_p2(const DevOptions &o, const VjpArgs &a, hipStream_t st
 {
 	return launch_vjp<PlanarTwoInput>(o, a, stream);
 }
+int launch_explicit_vjp_cp(const DevOptions &o, const VjpArgs &a, hipStream_t stream)
+{
+	return launch_vjp<CartPendulum>(o, a, stream);
+}
 
 } // namespace asif

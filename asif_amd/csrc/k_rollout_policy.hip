@@ -24,6 +24,9 @@
 // and LAUNCH on top of that: 8 bytes read per parameter given, 8 written per parameter gradient asked for.
 // SoA, every load and store a coalesced line; no LDS, no scratch, no register array indexed by a run-time value.  Lanes
 // beyond B repeat instance B-1 for the solver's votes and never store.
+// Models: DoubleIntegrator and CartPendulum (one input, functors that do not read DevOptions); the launchers at the end
+// dispatch on the handle's model.  A model with kJointFunctors (CartPendulum: one sine / cosine pair per step) is called
+// through its joint forms, model_step_functors / model_adjoint_functors of rollout_vjp_step.hpp.
 #include <cstdint>
 #include "launchers.hpp"
 #include "rollout_params_step.hpp"
@@ -108,8 +111,7 @@ __global__ __launch_bounds__(256) void rollout_policy_kernel(RolloutVjpOpts<M::N
 		double uDes[NU];
 		policy_udes<NX, NU>(kk, K, hasK, x, v, hasV, uDes);
 		double h[NP], Dh[NP * NX], f[NX], gm[NX * NU];
-		M::safetySet(o, x, h, Dh);
-		M::dynamics(o, x, f, gm);
+		model_step_functors<M>(o, x, h, Dh, f, gm);
 		QpLaneData<NV, NC> qp;
 		explicit_step_qp<NX, NU, NP>(h, Dh, f, gm, uDes, el, qp);
 		double sol[NV];
@@ -256,10 +258,9 @@ __global__ __launch_bounds__(256) void rollout_policy_vjp_kernel(RolloutVjpOpts<
 	a.nskip[i] = p.s.nskip;
 }
 
-template <bool PARAMS>
+template <class M, bool PARAMS>
 static int launch_forward(const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream)
 {
-	using M = DoubleIntegrator;
 	if (a.p.B <= 0 || a.p.T <= 0) return 0;
 	const dim3 grid(grid_for(a.p.B, 1, 256)), block(256);
 	const RolloutVjpOpts<M::NU> e = rollout_class_opts<M>(o);
@@ -268,39 +269,56 @@ static int launch_forward(const DevOptions &o, const ParamRolloutArgs &a, hipStr
 	return (int)hipGetLastError();
 }
 
-template <bool PARAMS, bool WANTP>
+template <class M, bool PARAMS, bool WANTP>
 static int launch_backward(const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream)
 {
-	using M = DoubleIntegrator;
 	if (a.p.B <= 0) return 0;
 	hipLaunchKernelGGL((rollout_policy_vjp_kernel<M, PARAMS, WANTP>), dim3(grid_for(a.p.B, 1, 256)), dim3(256), 0, stream,
 	                   rollout_class_opts<M>(o), a);
 	return (int)hipGetLastError();
 }
 
-int launch_rollout_policy_explicit_di(const DevOptions &o, const PolicyRolloutArgs &a, hipStream_t stream)
+// the models these rollouts are compiled for: one input, functors that do not read DevOptions.  f is called with a value
+// of the model's type
+template <class F>
+static int with_rollout_model(int model, F &&f)
 {
-	return launch_forward<false>(o, ParamRolloutArgs{a, nullptr, nullptr, nullptr}, stream);
+	switch (model) {
+	case ASIF_HIP_MODEL_DOUBLE_INTEGRATOR: return f(DoubleIntegrator{});
+	case ASIF_HIP_MODEL_CART_PENDULUM: return f(CartPendulum{});
+	default: return ASIF_HIP_EUNSUPPORTED;
+	}
+}
+
+int launch_rollout_policy_explicit(int model, const DevOptions &o, const PolicyRolloutArgs &a, hipStream_t stream)
+{
+	return with_rollout_model(model, [&](auto m) {
+		return launch_forward<decltype(m), false>(o, ParamRolloutArgs{a, nullptr, nullptr, nullptr}, stream);
+	});
 }
 
 // T == 0 runs the kernel too: it writes the identity (gx0 = gxT, guact0 = guactT or 0, gk = 0, gK = 0, nskip = 0, no gv)
-int launch_rollout_policy_vjp_explicit_di(const DevOptions &o, const PolicyRolloutVjpArgs &a, hipStream_t stream)
+int launch_rollout_policy_vjp_explicit(int model, const DevOptions &o, const PolicyRolloutVjpArgs &a, hipStream_t stream)
 {
-	return launch_backward<false, false>(
-		o, ParamRolloutVjpArgs{a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, stream);
+	return with_rollout_model(model, [&](auto m) {
+		return launch_backward<decltype(m), false, false>(
+			o, ParamRolloutVjpArgs{a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, stream);
+	});
 }
 
 // the PARAMS kernels also where all three parameters are absent
-int launch_rollout_params_explicit_di(const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream)
+int launch_rollout_params_explicit(int model, const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream)
 {
-	return launch_forward<true>(o, a, stream);
+	return with_rollout_model(model, [&](auto m) { return launch_forward<decltype(m), true>(o, a, stream); });
 }
 
-// T == 0: the identity of launch_rollout_policy_vjp_explicit_di, and galpha = glb = gub = 0
-int launch_rollout_params_vjp_explicit_di(const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream)
+// T == 0: the identity of launch_rollout_policy_vjp_explicit, and galpha = glb = gub = 0
+int launch_rollout_params_vjp_explicit(int model, const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream)
 {
-	if (a.galpha || a.glb || a.gub) return launch_backward<true, true>(o, a, stream);
-	return launch_backward<true, false>(o, a, stream);
+	return with_rollout_model(model, [&](auto m) {
+		if (a.galpha || a.glb || a.gub) return launch_backward<decltype(m), true, true>(o, a, stream);
+		return launch_backward<decltype(m), true, false>(o, a, stream);
+	});
 }
 
 } // namespace asif

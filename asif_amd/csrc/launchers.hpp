@@ -33,10 +33,12 @@ struct FilterArgs {
 	int fuseQp;
 };
 
-// explicit CBF filter (class ASIF), model = DoubleIntegrator / PlanarTwoInput
+// explicit CBF filter (class ASIF), model = DoubleIntegrator / PlanarTwoInput / CartPendulum
 int launch_explicit_di(const DevOptions &o, const asif_hip_solver &S, const FilterArgs &a, bool assemble_only,
                        hipStream_t stream);
 int launch_explicit_p2(const DevOptions &o, const asif_hip_solver &S, const FilterArgs &a, bool assemble_only,
+                       hipStream_t stream);
+int launch_explicit_cp(const DevOptions &o, const asif_hip_solver &S, const FilterArgs &a, bool assemble_only,
                        hipStream_t stream);
 
 // vector-Jacobian product of the explicit filter (k_explicit_vjp.hip): the gradient of a scalar loss with respect to
@@ -51,6 +53,7 @@ struct VjpArgs {
 };
 int launch_explicit_vjp_di(const DevOptions &o, const VjpArgs &a, hipStream_t stream);
 int launch_explicit_vjp_p2(const DevOptions &o, const VjpArgs &a, hipStream_t stream);
+int launch_explicit_vjp_cp(const DevOptions &o, const VjpArgs &a, hipStream_t stream);
 
 // closed loop: T x (explicit filter + plant Euler step) per launch, model = DoubleIntegrator
 struct RolloutArgs {
@@ -83,7 +86,8 @@ struct RolloutVjpArgs {
 	int32_t *nskip;               // [B] steps with rclog == 1 that the kernel's own solve did not decide
 };
 int launch_rollout_vjp_explicit_di(const DevOptions &o, const RolloutVjpArgs &a, hipStream_t stream);
-// the fused explicit rollout under an affine policy uDes_t = k + K x_t + v_t and its adjoint (k_rollout_policy.hip)
+// the fused explicit rollout under an affine policy uDes_t = k + K x_t + v_t and its adjoint (k_rollout_policy.hip);
+// model = DoubleIntegrator / CartPendulum (the four launchers dispatch on it; any other: ASIF_HIP_EUNSUPPORTED)
 struct PolicyRolloutArgs {
 	int64_t B, ld;
 	int T;
@@ -95,7 +99,7 @@ struct PolicyRolloutArgs {
 	double *xlog, *ulog;       // as RolloutArgs, each may be nullptr
 	int32_t *rclog;
 };
-int launch_rollout_policy_explicit_di(const DevOptions &o, const PolicyRolloutArgs &a, hipStream_t stream);
+int launch_rollout_policy_explicit(int model, const DevOptions &o, const PolicyRolloutArgs &a, hipStream_t stream);
 struct PolicyRolloutVjpArgs {
 	int64_t B, ld;
 	int T;
@@ -107,19 +111,19 @@ struct PolicyRolloutVjpArgs {
 	double *gx0, *gK, *gk, *gv, *guact0; // [nx][ld]; [nu*nx][ld] or nullptr; [nu][ld]; [T][nu][ld] or nullptr; [nu][ld]
 	int32_t *nskip;                      // [B]
 };
-int launch_rollout_policy_vjp_explicit_di(const DevOptions &o, const PolicyRolloutVjpArgs &a, hipStream_t stream);
+int launch_rollout_policy_vjp_explicit(int model, const DevOptions &o, const PolicyRolloutVjpArgs &a, hipStream_t stream);
 // the same rollout with the barrier gain and the input box per instance, and its adjoint (k_rollout_policy.hip, PARAMS)
 struct ParamRolloutArgs {
 	PolicyRolloutArgs p;
 	const double *alpha, *lb, *ub; // [B], [nu][ld], [nu][ld]; each may be nullptr: the handle's value
 };
-int launch_rollout_params_explicit_di(const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream);
+int launch_rollout_params_explicit(int model, const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream);
 struct ParamRolloutVjpArgs {
 	PolicyRolloutVjpArgs p;
 	const double *alpha, *lb, *ub; // as ParamRolloutArgs
 	double *galpha, *glb, *gub;    // [B], [nu][ld], [nu][ld]; each may be nullptr: not wanted
 };
-int launch_rollout_params_vjp_explicit_di(const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream);
+int launch_rollout_params_vjp_explicit(int model, const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream);
 // plant Euler step x += dt (f(x) + g(x) uact) between two filter calls of the two-stage filters (k_rollout.hip);
 // logs the state / input / rc of the call just made (nullptr to skip) and counts rc < 0 into nfail
 int launch_plant_step(int model, const DevOptions &o, int64_t B, int64_t ld, double dt, double *x, const double *uact,

@@ -590,6 +590,119 @@ struct PlanarTwoInput {
 };
 
 // ---------------------------------------------------------------------------------------------
+// Synthetic cart-driven pendulum for class ASIF.  NOT one of the reference's examples; it exists so that the differentiable
+// rollouts have a genuinely nonlinear plant: a pendulum about its upright whose pivot the input accelerates horizontally,
+// time normalised, x = (theta, omega),
+//     f = (omega, sin theta),  g = (0, -cos theta),  Df = [0 1; cos theta 0],  d g_1 / d theta = sin theta
+// so that Dg, the mixed entries of D2h and the state-dependent Df of rollout_vjp_step.hpp are all non-zero.  Safety set:
+// the double integrator's braking parabolas on theta (rows 0, 1), an ellipse with a cross term (row 2) and the energy-like
+// cos theta - omega^2 / 2 (row 3).
+// One step needs ONE sine / cosine pair: every functor takes it from trig(), and the joint forms (kJointFunctors:
+// stepFunctors for a forward step, adjointFunctors for a step of the adjoint; rollout_vjp_step.hpp) evaluate it once for
+// all the functors of a step.  The library's sincos, every product rounded on its own (fp contract off): the forward and
+// the backward kernels, and the filter entries next to them, see the same bits.
+struct CartPendulum {
+	static constexpr bool kIgnoresOptions = true; // no functor below reads DevOptions (k_explicit.hip: explicit_light_kernel)
+	static constexpr int NX = 2, NU = 1, NPSS = 4;
+	static constexpr bool kJointFunctors = true;
+
+	__device__ static void trig(const double (&x)[NX], double &s, double &c) { sincos(x[0], &s, &c); }
+
+	__device__ static void safetySetAt(double s, double c, const double (&x)[NX], double (&h)[NPSS], double (&Dh)[NPSS * NX])
+	{
+#pragma clang fp contract(off)
+		const double brake = (x[1] * x[1]) / 2.0;
+		const bool fwd = x[1] > 0;
+		h[0] = fwd ? (1.0 - x[0] - brake) : (-x[0] + 1.0);
+		h[1] = fwd ? (x[0] + 1.0) : (x[0] + 1.0 - brake);
+		h[2] = 1.5 - ((x[0] * x[0] + x[0] * x[1]) + x[1] * x[1]);
+		h[3] = c - brake;
+		Dh[0] = -1.0;                     Dh[4] = fwd ? -x[1] : 0.0;
+		Dh[1] = 1.0;                      Dh[5] = fwd ? 0.0 : -x[1];
+		Dh[2] = -(2.0 * x[0] + x[1]);     Dh[6] = -(x[0] + 2.0 * x[1]);
+		Dh[3] = -s;                       Dh[7] = -x[1];
+	}
+	__device__ static void dynamicsAt(double s, double c, const double (&x)[NX], double (&f)[NX], double (&g)[NX * NU])
+	{
+		f[0] = x[1];
+		f[1] = s;
+		g[0] = 0.0;
+		g[1] = -c;
+	}
+	// D2h[r + NPSS * (k + NX * m)] = d2 h_r / dx_k dx_m on the branch safetySet takes
+	__device__ static void safetyHessAt(double, double c, const double (&x)[NX], double (&D2h)[NPSS * NX * NX])
+	{
+		const bool fwd = x[1] > 0;
+#pragma unroll
+		for (int k = 0; k < NPSS * NX * NX; k++) D2h[k] = 0.0;
+		D2h[0 + NPSS * (1 + NX * 1)] = fwd ? -1.0 : 0.0;
+		D2h[1 + NPSS * (1 + NX * 1)] = fwd ? 0.0 : -1.0;
+		D2h[2 + NPSS * (0 + NX * 0)] = -2.0;
+		D2h[2 + NPSS * (1 + NX * 0)] = -1.0;
+		D2h[2 + NPSS * (0 + NX * 1)] = -1.0;
+		D2h[2 + NPSS * (1 + NX * 1)] = -2.0;
+		D2h[3 + NPSS * (0 + NX * 0)] = -c;
+		D2h[3 + NPSS * (1 + NX * 1)] = -1.0;
+	}
+	// Df[k + m * NX] = d f_k / dx_m;  Dg[k + m * NX + j * NX * NX] = d g_{k,j} / dx_m
+	__device__ static void dynamicsJacAt(double s, double c, double (&Df)[NX * NX], double (&Dg)[NX * NX * NU])
+	{
+		Df[0] = 0.0; Df[2] = 1.0;
+		Df[1] = c;   Df[3] = 0.0;
+#pragma unroll
+		for (int k = 0; k < NX * NX * NU; k++) Dg[k] = 0.0;
+		Dg[1] = s;
+	}
+
+	// the four functors in the layouts the double integrator documents
+	__device__ static void safetySet(const DevOptions &, const double (&x)[NX], double (&h)[NPSS], double (&Dh)[NPSS * NX])
+	{
+		double s, c;
+		trig(x, s, c);
+		safetySetAt(s, c, x, h, Dh);
+	}
+	__device__ static void dynamics(const DevOptions &, const double (&x)[NX], double (&f)[NX], double (&g)[NX * NU])
+	{
+		double s, c;
+		trig(x, s, c);
+		dynamicsAt(s, c, x, f, g);
+	}
+	__device__ static void safetyHess(const DevOptions &, const double (&x)[NX], double (&D2h)[NPSS * NX * NX])
+	{
+		double s, c;
+		trig(x, s, c);
+		safetyHessAt(s, c, x, D2h);
+	}
+	__device__ static void dynamicsJac(const DevOptions &, const double (&x)[NX], double (&Df)[NX * NX],
+	                                   double (&Dg)[NX * NX * NU])
+	{
+		double s, c;
+		trig(x, s, c);
+		dynamicsJacAt(s, c, Df, Dg);
+	}
+	// ... and the joint forms: what a step of the forward loop and a step of the adjoint call, on one pair
+	__device__ static void stepFunctors(const DevOptions &, const double (&x)[NX], double (&h)[NPSS], double (&Dh)[NPSS * NX],
+	                                    double (&f)[NX], double (&g)[NX * NU])
+	{
+		double s, c;
+		trig(x, s, c);
+		safetySetAt(s, c, x, h, Dh);
+		dynamicsAt(s, c, x, f, g);
+	}
+	__device__ static void adjointFunctors(const DevOptions &, const double (&x)[NX], double (&h)[NPSS],
+	                                       double (&Dh)[NPSS * NX], double (&f)[NX], double (&g)[NX * NU],
+	                                       double (&D2h)[NPSS * NX * NX], double (&Df)[NX * NX], double (&Dg)[NX * NX * NU])
+	{
+		double s, c;
+		trig(x, s, c);
+		safetySetAt(s, c, x, h, Dh);
+		dynamicsAt(s, c, x, f, g);
+		safetyHessAt(s, c, x, D2h);
+		dynamicsJacAt(s, c, Df, Dg);
+	}
+};
+
+// ---------------------------------------------------------------------------------------------
 // Double integrator with an LQR-like backup controller, examples/DoubleIntegrator_implicit.cpp:13-90:
 // plain box |x|,|v| <= 1 (not the braking parabola of examples/DoubleIntegrator.cpp), ellipsoidal backup set.
 // Sums are accumulated from 0.0 like the reference's matrixVectorMultiply (include/asif_utils.h:46-62).

@@ -24,10 +24,11 @@
 // rc is the caller's record of what the forward pass decided.  rc == 1 next to a solve of this file that does not end
 // optimal (not possible on the same code and the same bits) contributes nothing: mu = 0 and the step is counted.
 //
-// M supplies safetySet, dynamics, safetyHess and dynamicsJac (models.hpp); O is whatever those functors take as their
-// first argument.  Like gi_small.hpp the file compiles for the host: tests/host_rollout_vjp_driver.cpp runs it on the
+// M supplies safetySet, dynamics, safetyHess and dynamicsJac (models.hpp) or, where it declares kJointFunctors, their joint
+// forms (model_adjoint_functors below); O is whatever those functors take as their first argument.  Like gi_small.hpp the file compiles for the host: tests/host_rollout_vjp_driver.cpp runs it on the
 // CPU with a plain C++ copy of the model's functors.  No loop indexes a register array by a run-time value.
 #pragma once
+#include <type_traits>
 #include "gi_small.hpp"
 
 namespace asif {
@@ -105,6 +106,42 @@ ASIF_HD void explicit_step_qp(const double (&h)[NP], const double (&Dh)[NP * NX]
 	qp.ub[NU] = e.relaxLb;
 }
 
+// A model whose functors share work at a state (the cart-driven pendulum: one sine / cosine pair) declares
+// kJointFunctors and supplies stepFunctors (safetySet + dynamics) and adjointFunctors (all four) -- the same values as
+// the four functors one by one, evaluated together.  Every other model is called functor by functor, as before.
+template <class M, class = void>
+struct joint_functors : std::false_type {};
+template <class M>
+struct joint_functors<M, std::enable_if_t<M::kJointFunctors>> : std::true_type {};
+
+template <class M, class O>
+ASIF_HD void model_step_functors(const O &o, const double (&x)[M::NX], double (&h)[M::NPSS], double (&Dh)[M::NPSS * M::NX],
+                                 double (&f)[M::NX], double (&gm)[M::NX * M::NU])
+{
+	if constexpr (joint_functors<M>::value) {
+		M::stepFunctors(o, x, h, Dh, f, gm);
+	} else {
+		M::safetySet(o, x, h, Dh);
+		M::dynamics(o, x, f, gm);
+	}
+}
+
+template <class M, class O>
+ASIF_HD void model_adjoint_functors(const O &o, const double (&x)[M::NX], double (&h)[M::NPSS],
+                                    double (&Dh)[M::NPSS * M::NX], double (&f)[M::NX], double (&gm)[M::NX * M::NU],
+                                    double (&D2h)[M::NPSS * M::NX * M::NX], double (&Df)[M::NX * M::NX],
+                                    double (&Dg)[M::NX * M::NX * M::NU])
+{
+	if constexpr (joint_functors<M>::value) {
+		M::adjointFunctors(o, x, h, Dh, f, gm, D2h, Df, Dg);
+	} else {
+		M::safetySet(o, x, h, Dh);
+		M::dynamics(o, x, f, gm);
+		M::safetyHess(o, x, D2h);
+		M::dynamicsJac(o, x, Df, Dg);
+	}
+}
+
 template <class M>
 struct RolloutAdjoint { // what the sweep carries from step to step
 	double lam[M::NX], mu[M::NU], gudes[M::NU];
@@ -126,10 +163,7 @@ ASIF_HD void rollout_vjp_step(const O &o, const RolloutVjpOpts<M::NU> &e, double
 	constexpr int NX = M::NX, NU = M::NU, NP = M::NPSS, NV = NU + 1, NC = NP;
 	static_assert(NU == 1 || NU == 2, "closed-form adjoint: 1 x 1 or 2 x 2");
 	double h[NP], Dh[NP * NX], f[NX], gm[NX * NU], D2h[NP * NX * NX], Df[NX * NX], Dg[NX * NX * NU];
-	M::safetySet(o, x, h, Dh);
-	M::dynamics(o, x, f, gm);
-	M::safetyHess(o, x, D2h);
-	M::dynamicsJac(o, x, Df, Dg);
+	model_adjoint_functors<M>(o, x, h, Dh, f, gm, D2h, Df, Dg);
 
 	// ---- 1. the plant's Euler step backwards
 	double lamn[NX];

@@ -4,8 +4,10 @@ The explicit safety filter (class ASIF).  Forward: asif_hip_filter_batch / asif_
 asif_hip_filter_vjp_batch launch (asif_amd/csrc/k_explicit_vjp.hip).
 The fused explicit rollout, T x (filter + plant Euler step) on the double integrator.  Forward: asif_hip_rollout_batch.
 Backward: one asif_hip_rollout_vjp_batch launch (asif_amd/csrc/k_rollout_vjp.hip), state gradient included.
-The same rollout under an affine policy udes_t = k + K x_t + v_t evaluated inside the loop.  Forward:
-asif_hip_rollout_policy_batch.  Backward: one asif_hip_rollout_policy_vjp_batch launch (asif_amd/csrc/k_rollout_policy.hip).
+The same rollout under an affine policy udes_t = k + K x_t + v_t evaluated inside the loop, on the double integrator or
+the cart-driven pendulum (capi.MODEL_CART_PENDULUM, a nonlinear plant), optionally with the barrier gain and the input box
+per instance.  Forward: asif_hip_rollout_policy_batch / asif_hip_rollout_params_batch.  Backward: one
+asif_hip_rollout_policy_vjp_batch / asif_hip_rollout_params_vjp_batch launch (asif_amd/csrc/k_rollout_policy.hip).
 The batched solve of small pre-assembled QPs.  Forward: asif_hip_qp_solve_batch.  Backward: one asif_hip_qp_vjp_batch
 launch (asif_amd/csrc/k_qp_vjp.hip).
 All of it runs on torch's current stream; nothing here computes on the CPU, and no solve or adjoint falls back to torch
@@ -18,6 +20,10 @@ Hd, c, lb, ub [nv,B], A [nc*nv,B] (entry (r, j) of the row matrix at component r
 import torch
 
 from . import capi
+
+
+# the models the fused rollouts under a policy (PolicyRolloutFn, ParamRolloutFn) are compiled for
+ROLLOUT_MODELS = (capi.MODEL_DOUBLE_INTEGRATOR, capi.MODEL_CART_PENDULUM)
 
 
 def _soa(t, rows, B, name):
@@ -112,7 +118,8 @@ class ExplicitRolloutFn(torch.autograd.Function):
         if T < 0:
             raise ValueError(f"T: expected a non-negative step count, got {T}")
         if flt.model != capi.MODEL_DOUBLE_INTEGRATOR or flt.variant != capi.EXPLICIT:
-            raise ValueError("the differentiable rollout exists for the explicit filter on the double integrator only")
+            raise ValueError("the differentiable rollout with udes held exists for the explicit filter on the double "
+                             "integrator only; on the cart-driven pendulum use PolicyRolloutFn with K = v = None")
         x = _soa(x0, d.nx, B, "x0").clone()
         udes = _soa(udes, d.nu, B, "udes")
         uact = (_soa(uact_prev, d.nu, B, "uact_prev").clone() if uact_prev is not None
@@ -166,7 +173,8 @@ class ExplicitRolloutLayer(torch.nn.Module):
 class PolicyRolloutFn(torch.autograd.Function):
     """xT, uactT, xlog, ulog, rclog, nfail = PolicyRolloutFn.apply(flt, x0, k, K, v, uact_prev, T, dt)
 
-    ExplicitRolloutFn with the desired input coming from an affine policy evaluated inside the loop:
+    ExplicitRolloutFn with the desired input coming from an affine policy evaluated inside the loop, on the double
+    integrator or the cart-driven pendulum (flt: an explicit capi.Filter on one of ROLLOUT_MODELS):
     udes_t = k + K x_t + v_t.  k [nu,B]; K [nu*nx,B] (entry (j, m) of an instance's gain at component j + m*nu) or None;
     v [T,nu,B] (a planned input sequence) or None; an absent term is not evaluated.  uact_prev and the outputs as
     ExplicitRolloutFn.  Gradients flow to x0, k, K, v and uact_prev from xT, uactT, xlog and ulog.  Forward is one
@@ -183,8 +191,9 @@ class PolicyRolloutFn(torch.autograd.Function):
         T = int(T)
         if T < 0:
             raise ValueError(f"T: expected a non-negative step count, got {T}")
-        if flt.model != capi.MODEL_DOUBLE_INTEGRATOR or flt.variant != capi.EXPLICIT:
-            raise ValueError("the differentiable rollout exists for the explicit filter on the double integrator only")
+        if flt.model not in ROLLOUT_MODELS or flt.variant != capi.EXPLICIT:
+            raise ValueError("the differentiable rollout under a policy exists for the explicit filter on the double "
+                             "integrator and on the cart-driven pendulum")
         x = _soa(x0, d.nx, B, "x0").clone()
         k = _soa(k, d.nu, B, "k")
         K = _soa(K, d.nu * d.nx, B, "K") if K is not None else None
@@ -264,8 +273,9 @@ class ParamRolloutFn(torch.autograd.Function):
         T = int(T)
         if T < 0:
             raise ValueError(f"T: expected a non-negative step count, got {T}")
-        if flt.model != capi.MODEL_DOUBLE_INTEGRATOR or flt.variant != capi.EXPLICIT:
-            raise ValueError("the differentiable rollout exists for the explicit filter on the double integrator only")
+        if flt.model not in ROLLOUT_MODELS or flt.variant != capi.EXPLICIT:
+            raise ValueError("the differentiable rollout under a policy exists for the explicit filter on the double "
+                             "integrator and on the cart-driven pendulum")
         x = _soa(x0, d.nx, B, "x0").clone()
         k = _soa(k, d.nu, B, "k")
         K = _soa(K, d.nu * d.nx, B, "K") if K is not None else None

@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define ASIF_HIP_VERSION 180 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
+#define ASIF_HIP_VERSION 190 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
                               * 120: ASIF_HIP_IMPLICIT_RB (options grew at the end), asif_hip_set_learning, asif_hip_affine_replay;
                               * 130: solver.adaptive_rho_interval (struct grew at the end), polish == 2 is the dual active-set
                               *      stage of gi_small.hpp;
@@ -61,7 +61,9 @@ extern "C" {
                               * 170: asif_hip_rollout_policy_batch / asif_hip_rollout_policy_vjp_batch, the fused explicit rollout
                               *      and its adjoint under an affine policy uDes_t = k + K x_t + v_t evaluated inside the loop;
                               * 180: asif_hip_rollout_params_batch / asif_hip_rollout_params_vjp_batch, that rollout and its adjoint
-                              *      with the barrier gain and the input box per instance, and their gradients */
+                              *      with the barrier gain and the input box per instance, and their gradients;
+                              * 190: ASIF_HIP_MODEL_CART_PENDULUM, a synthetic nonlinear one-input model: explicit handles, the
+                              *      filter's vector-Jacobian product and the four policy / params rollout entries */
 
 enum asif_hip_error {
 	ASIF_HIP_OK = 0,
@@ -84,7 +86,12 @@ enum asif_hip_model {
 	ASIF_HIP_MODEL_PLANAR_TWO_INPUT = 8, /* NOT an example of the reference: synthetic nx = 2, nu = 2 model (x' = Fx + Gu,
 	                                      * five half-planes) so that class ASIF's nu > 1 code (src/asif.cpp:279-303,
 	                                      * 314-352) has a device path and a parity test */
-	ASIF_HIP_MODEL_DOUBLE_INTEGRATOR_TB = 9 /* examples/DoubleIntegrator_implicit_tb.cpp:13-103 (ASIF_HIP_IMPLICIT_TB) */
+	ASIF_HIP_MODEL_DOUBLE_INTEGRATOR_TB = 9, /* examples/DoubleIntegrator_implicit_tb.cpp:13-103 (ASIF_HIP_IMPLICIT_TB) */
+	ASIF_HIP_MODEL_CART_PENDULUM = 10 /* NOT an example of the reference: synthetic nx = 2, nu = 1 model, a pendulum about its
+	                                   * upright whose pivot the input accelerates (f = (omega, sin theta), g = (0, -cos theta),
+	                                   * four curved safety functions), so that the differentiable rollouts have a nonlinear
+	                                   * plant: Dg, a state-dependent Df and mixed second derivatives of h.  ASIF_HIP_EXPLICIT
+	                                   * only; input box [-4, 4] by default */
 };
 
 enum asif_hip_variant {
@@ -320,8 +327,9 @@ int asif_hip_filter_batch_lie(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const d
  *   rc[i]: 1 gradient of a solved instance; -1 the forward QP is infeasible or its data are non-finite (filter() left
  *   uAct untouched: dL/duAct passes to whatever uAct held before); 0 the exact stage left it undecided.  For -1 and 0
  *   every gradient slot of the instance is written as 0.  Every gradient slot of every instance i < B is written.
- * Explicit handles on DOUBLE_INTEGRATOR and PLANAR_TWO_INPUT with the default solver mode (polish == 2, with or without
- * presolve; lanes_per_qp 0 or 1); anything else: ASIF_HIP_EUNSUPPORTED.  The handle's forward results do not change. */
+ * Explicit handles on DOUBLE_INTEGRATOR, PLANAR_TWO_INPUT and CART_PENDULUM with the default solver mode (polish == 2, with
+ * or without presolve; lanes_per_qp 0 or 1); anything else: ASIF_HIP_EUNSUPPORTED.  The handle's forward results do not
+ * change. */
 int asif_hip_filter_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, const double *udes,
                               const double *lfh, const double *lgh, const double *guact, double *gudes, double *glfh,
                               double *glgh, double *gx, int32_t *rc, void *stream);
@@ -336,12 +344,14 @@ int asif_hip_filter_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const d
  * ASIF on ASIF_HIP_MODEL_DOUBLE_INTEGRATOR: one fused kernel for the whole rollout.  ASIFimplicit / ASIFimplicitRB /
  * ASIFimplicitTB handles (examples/InvertedPendulum_Implicit.cpp:113-136 and the like): T x (rows kernel, QP kernel,
  * plant-step kernel) queued on `stream` with no host round trip; a failed call applies what filter() wrote to uAct
- * (the saturated backup controller), as those examples do.  Other handles: ASIF_HIP_EUNSUPPORTED. */
+ * (the saturated backup controller), as those examples do.  Other handles: ASIF_HIP_EUNSUPPORTED -- explicit handles on
+ * ASIF_HIP_MODEL_CART_PENDULUM among them: asif_hip_rollout_policy_batch with K = v = NULL is the plain rollout there. */
 int asif_hip_rollout_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, double *x,
                            const double *udes, double *uact, double *relax, int32_t *nfail, double *xlog,
                            double *ulog, int32_t *rclog, void *stream);
 
-/* The fused explicit rollout backwards (class ASIF on ASIF_HIP_MODEL_DOUBLE_INTEGRATOR; no counterpart in the reference):
+/* The fused explicit rollout backwards (class ASIF on ASIF_HIP_MODEL_DOUBLE_INTEGRATOR alone -- on
+ * ASIF_HIP_MODEL_CART_PENDULUM asif_hip_rollout_policy_vjp_batch with K = v = NULL is this sweep; no counterpart in the reference):
  * the gradient of a scalar loss L through T x (filter + plant Euler step), in one launch.  The forward pass is, for
  * t = 0 ... T-1 with u_{-1} the uact handed in,
  *     xlog[t] = x_t;   (ok_t, u*_t) = filter(x_t, udes);   u_t = ok_t ? u*_t : u_{t-1};   ulog[t] = u_t;
@@ -375,18 +385,19 @@ int asif_hip_rollout_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_
                                const double *guactT, const double *gxlog, const double *gulog, double *gx0,
                                double *gudes, double *guact0, int32_t *nskip, void *stream);
 
-/* The fused explicit rollout under an affine policy (class ASIF on ASIF_HIP_MODEL_DOUBLE_INTEGRATOR; no counterpart in the
- * reference): asif_hip_rollout_batch's fused path with the desired input evaluated inside the loop.  For t = 0 ... T-1,
+/* The fused explicit rollout under an affine policy (class ASIF on ASIF_HIP_MODEL_DOUBLE_INTEGRATOR or
+ * ASIF_HIP_MODEL_CART_PENDULUM; no counterpart in the reference): asif_hip_rollout_batch's fused path with the desired input evaluated inside the loop.  For t = 0 ... T-1,
  * with u_{-1} the uact handed in,
  *     uDes_t = k + K x_t + v_t;   (ok_t, u*_t) = filter(x_t, uDes_t);   u_t = ok_t ? u*_t : u_{t-1};
  *     x_{t+1} = x_t + dt (f(x_t) + g(x_t) u_t)
  * uDes_t,j is formed in one order, without contraction: k_j, plus K[j,m] x_t,m for m = 0 ... nx-1, plus v_t,j.
  *   K[nu*nx][ldx], entry (j, m) at component j + m nu: per-instance feedback gains, or NULL;  k[nu][ldx];
  *   v[T][nu][ldx]: a planned input sequence, or NULL.  A NULL term is not evaluated at all: with K = v = NULL every output
- *   equals asif_hip_rollout_batch's with udes = k, bit for bit.
+ *   equals asif_hip_rollout_batch's with udes = k, bit for bit (on the double integrator, the one model that entry's fused
+ *   path has).
  *   x, uact, relax, nfail, xlog, ulog, rclog: as asif_hip_rollout_batch (the three logs may be NULL).
- * Explicit handles on DOUBLE_INTEGRATOR whose solver mode is the dual active-set stage (polish == 2, or presolve;
- * lanes_per_qp 0 or 1), any npSSmax; anything else: ASIF_HIP_EUNSUPPORTED.  A NULL required pointer, ldx < B, T < 0 or
+ * Explicit handles on DOUBLE_INTEGRATOR or CART_PENDULUM whose solver mode is the dual active-set stage (polish == 2, or
+ * presolve; lanes_per_qp 0 or 1), any npSSmax; anything else: ASIF_HIP_EUNSUPPORTED.  A NULL required pointer, ldx < B, T < 0 or
  * B < 0: ASIF_HIP_EINVAL.  B == 0 or T == 0 returns ASIF_HIP_OK and touches nothing. */
 int asif_hip_rollout_policy_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, double *x,
                                   const double *K, const double *k, const double *v, double *uact, double *relax,
@@ -402,8 +413,9 @@ int asif_hip_rollout_policy_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int
  *   gx0[nx][ldx], gk[nu][ldx], guact0[nu][ldx], nskip int32[B] out;  gK[nu*nx][ldx], gv[T][nu][ldx] out, each may be NULL
  *   (not wanted).  gK without K or gv without v: ASIF_HIP_EINVAL.  Every slot of every instance i < B is written.
  *   T == 0 is the identity: gx0 = gxT, guact0 = guactT (or 0), gk = gK = 0, nskip = 0, gv untouched.
- * Handles, refusals and nskip as asif_hip_rollout_vjp_batch.  With K = v = NULL, gx0, guact0, nskip and gk equal that
- * entry's gx0, guact0, nskip and gudes bit for bit.  The handle's forward results do not change. */
+ * Explicit handles on DOUBLE_INTEGRATOR or CART_PENDULUM; solver modes, refusals and nskip as asif_hip_rollout_vjp_batch.
+ * With K = v = NULL, gx0, guact0, nskip and gk equal that entry's gx0, guact0, nskip and gudes bit for bit (on the double
+ * integrator, the model that entry has).  The handle's forward results do not change. */
 int asif_hip_rollout_policy_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, const double *xlog,
                                       const double *ulog, const int32_t *rclog, const double *K, const double *k,
                                       const double *v, const double *gxT, const double *guactT, const double *gxlog,
@@ -417,7 +429,8 @@ int asif_hip_rollout_policy_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx,
  * values, every output equals asif_hip_rollout_policy_batch's bit for bit.  relaxCost and npSSmax stay per handle.
  * The arrays are data: a gain handed in that is not a positive finite number, lb_i > ub_i or a non-finite bound make every
  * step of that instance fail (rclog -1, counted in nfail, u_t = u_{t-1}) and leave every other instance as it is.
- * Everything else -- handles, refusals, B == 0, T == 0 -- as asif_hip_rollout_policy_batch. */
+ * Everything else -- handles (explicit, on DOUBLE_INTEGRATOR or CART_PENDULUM), refusals, B == 0, T == 0 -- as
+ * asif_hip_rollout_policy_batch. */
 int asif_hip_rollout_params_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, double *x,
                                   const double *K, const double *k, const double *v, const double *alpha,
                                   const double *lb, const double *ub, double *uact, double *relax, int32_t *nfail,
@@ -431,8 +444,9 @@ int asif_hip_rollout_params_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int
  * (both equal mu_j, the gradient arriving at u_t).  A failed or free step adds nothing; kinks on the forward pass's side.
  *   alpha, lb, ub: as handed to the forward entry.  galpha without alpha, glb without lb, gub without ub: ASIF_HIP_EINVAL,
  *   like gK without K.  T == 0: the identity, and galpha = glb = gub = 0.
- * With the three parameters NULL every output equals asif_hip_rollout_policy_vjp_batch's bit for bit.  Everything else as
- * that entry.  The handle's forward results do not change. */
+ * With the three parameters NULL every output equals asif_hip_rollout_policy_vjp_batch's bit for bit.  Everything else,
+ * the handles (explicit, on DOUBLE_INTEGRATOR or CART_PENDULUM) included, as that entry.  The handle's forward results do
+ * not change. */
 int asif_hip_rollout_params_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, const double *xlog,
                                       const double *ulog, const int32_t *rclog, const double *K, const double *k,
                                       const double *v, const double *alpha, const double *lb, const double *ub,
