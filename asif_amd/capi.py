@@ -54,7 +54,12 @@ EXPORTS = [
     "asif_hip_math_probe", "asif_hip_qp_solve_batch_warm", "asif_hip_qp_vjp_batch", "asif_hip_rollout_vjp_batch",
     "asif_hip_rollout_policy_batch", "asif_hip_rollout_policy_vjp_batch",
     "asif_hip_rollout_params_batch", "asif_hip_rollout_params_vjp_batch",
+    "asif_hip_rollout_plant_batch", "asif_hip_rollout_plant_vjp_batch",
 ]
+
+# the plant's integrator of rollout_plant / rollout_plant_vjp (ASIF_HIP_PLANT_*): forward Euler, or a fourth-order
+# Runge-Kutta step with the input held over the control period
+PLANT_EULER, PLANT_RK4 = 0, 1
 
 MODEL_DOUBLE_INTEGRATOR_SAMPLED = 4
 MODEL_DOUBLE_INTEGRATOR_ROBUST = 5
@@ -177,6 +182,8 @@ def load():
         lib.asif_hip_rollout_policy_vjp_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double] + [vp] * 17
         lib.asif_hip_rollout_params_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double] + [vp] * 14
         lib.asif_hip_rollout_params_vjp_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double] + [vp] * 23
+        lib.asif_hip_rollout_plant_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double, C.c_int32] + [vp] * 14
+        lib.asif_hip_rollout_plant_vjp_batch.argtypes = [vp, i64, i64, C.c_int32, C.c_double, C.c_int32] + [vp] * 23
         _lib = lib
     return _lib
 
@@ -331,6 +338,30 @@ class Filter:
                                                          _ptr(ub), _ptr(gxT), _ptr(guactT), _ptr(gxlog), _ptr(gulog),
                                                          _ptr(gx0), _ptr(gK), _ptr(gk), _ptr(gv), _ptr(galpha),
                                                          _ptr(glb), _ptr(gub), _ptr(guact0), _ptr(nskip), _stream()))
+
+    def rollout_plant(self, T, dt, integrator, x, k, uact, relax, nfail, K=None, v=None, alpha=None, lb=None, ub=None,
+                      xlog=None, ulog=None, rclog=None):
+        """rollout_params() with the plant's integrator as an argument (asif_hip_rollout_plant_batch), one launch:
+        PLANT_EULER is rollout_params() bit for bit, PLANT_RK4 steps the plant with a fourth-order Runge-Kutta step
+        under the held input.  The filter is evaluated at the sample instants only."""
+        B = x.shape[1]
+        check(self.lib.asif_hip_rollout_plant_batch(self.handle, B, x.stride(0), T, dt, integrator, _ptr(x), _ptr(K),
+                                                    _ptr(k), _ptr(v), _ptr(alpha), _ptr(lb), _ptr(ub), _ptr(uact),
+                                                    _ptr(relax), _ptr(nfail), _ptr(xlog), _ptr(ulog), _ptr(rclog),
+                                                    _stream()))
+
+    def rollout_plant_vjp(self, T, dt, integrator, xlog, ulog, rclog, k, gxT, gx0, gk, guact0, nskip, K=None, v=None,
+                          alpha=None, lb=None, ub=None, guactT=None, gxlog=None, gulog=None, gK=None, gv=None,
+                          galpha=None, glb=None, gub=None):
+        """rollout_plant() backwards (asif_hip_rollout_plant_vjp_batch), one launch: rollout_params_vjp()'s arguments
+        and the integrator the forward pass used."""
+        B = gxT.shape[1]
+        check(self.lib.asif_hip_rollout_plant_vjp_batch(self.handle, B, gxT.stride(0), T, dt, integrator, _ptr(xlog),
+                                                        _ptr(ulog), _ptr(rclog), _ptr(K), _ptr(k), _ptr(v), _ptr(alpha),
+                                                        _ptr(lb), _ptr(ub), _ptr(gxT), _ptr(guactT), _ptr(gxlog),
+                                                        _ptr(gulog), _ptr(gx0), _ptr(gK), _ptr(gk), _ptr(gv),
+                                                        _ptr(galpha), _ptr(glb), _ptr(gub), _ptr(guact0), _ptr(nskip),
+                                                        _stream()))
 
     def assemble(self, x, A, b, code, diag=None):
         B = x.shape[1]

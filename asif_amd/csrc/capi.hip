@@ -1164,6 +1164,48 @@ extern "C" int asif_hip_rollout_params_vjp_batch(asif_hip_ctx *ctx, int64_t B, i
 	return launch_rollout_params_vjp_explicit(ctx->model, ctx->dev, a, (hipStream_t)stream);
 }
 
+// the params entries with the plant's integrator as an argument: the same checks in the same order, then the integrator
+extern "C" int asif_hip_rollout_plant_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt,
+                                            int32_t integrator, double *x, const double *K, const double *k,
+                                            const double *v, const double *alpha, const double *lb, const double *ub,
+                                            double *uact, double *relax, int32_t *nfail, double *xlog, double *ulog,
+                                            int32_t *rclog, void *stream)
+{
+	if (!ctx || B < 0 || ldx < B || T < 0 || (B > 0 && (!x || !k || !uact || !relax || !nfail))) return ASIF_HIP_EINVAL;
+	if (integrator != ASIF_HIP_PLANT_EULER && integrator != ASIF_HIP_PLANT_RK4) return ASIF_HIP_EINVAL;
+	if (int r = policy_rollout_handle(ctx, true)) return r;
+	if (B == 0 || T == 0) return ASIF_HIP_OK;
+	hipError_t e = hipSetDevice(ctx->device);
+	if (e != hipSuccess) return (int)e;
+	const ParamRolloutArgs a = {{B, ldx, T, dt, x, K, k, v, uact, relax, nfail, xlog, ulog, rclog}, alpha, lb, ub};
+	return launch_rollout_plant_explicit(ctx->model, integrator, ctx->dev, a, (hipStream_t)stream);
+}
+
+extern "C" int asif_hip_rollout_plant_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt,
+                                                int32_t integrator, const double *xlog, const double *ulog,
+                                                const int32_t *rclog, const double *K, const double *k, const double *v,
+                                                const double *alpha, const double *lb, const double *ub,
+                                                const double *gxT, const double *guactT, const double *gxlog,
+                                                const double *gulog, double *gx0, double *gK, double *gk, double *gv,
+                                                double *galpha, double *glb, double *gub, double *guact0, int32_t *nskip,
+                                                void *stream)
+{
+	if (!ctx || B < 0 || ldx < B || T < 0) return ASIF_HIP_EINVAL;
+	if (integrator != ASIF_HIP_PLANT_EULER && integrator != ASIF_HIP_PLANT_RK4) return ASIF_HIP_EINVAL;
+	if (B > 0 && (!k || !gxT || !gx0 || !gk || !guact0 || !nskip)) return ASIF_HIP_EINVAL;
+	if (B > 0 && T > 0 && (!xlog || !ulog || !rclog)) return ASIF_HIP_EINVAL; // no step, no log to read
+	if ((gK && !K) || (gv && !v)) return ASIF_HIP_EINVAL;                     // a gradient of a term that is not there
+	if ((galpha && !alpha) || (glb && !lb) || (gub && !ub)) return ASIF_HIP_EINVAL; // ... or of a parameter not given
+	if (int r = policy_rollout_handle(ctx, false)) return r; // the sweep repeats each step's solve in the default mode
+	if (B == 0) return ASIF_HIP_OK;
+	hipError_t e = hipSetDevice(ctx->device);
+	if (e != hipSuccess) return (int)e;
+	const ParamRolloutVjpArgs a = {{B,   ldx,    T,     dt,    xlog, ulog, rclog, K,  k,      v,
+	                                gxT, guactT, gxlog, gulog, gx0,  gK,   gk,    gv, guact0, nskip},
+	                               alpha, lb, ub, galpha, glb, gub};
+	return launch_rollout_plant_vjp_explicit(ctx->model, integrator, ctx->dev, a, (hipStream_t)stream);
+}
+
 extern "C" int asif_hip_assemble_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, double *A,
                                        double *b, int32_t *code, double *diag, void *stream)
 {

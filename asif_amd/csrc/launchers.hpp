@@ -124,6 +124,12 @@ struct ParamRolloutVjpArgs {
 	double *galpha, *glb, *gub;    // [B], [nu][ld], [nu][ld]; each may be nullptr: not wanted
 };
 int launch_rollout_params_vjp_explicit(int model, const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream);
+// the params rollout and its adjoint with the plant's integrator as an argument (k_rollout_plant.hip): ASIF_HIP_PLANT_EULER
+// is the two launchers above, ASIF_HIP_PLANT_RK4 the RK4 instantiations; any other integrator: ASIF_HIP_EINVAL
+int launch_rollout_plant_explicit(int model, int integrator, const DevOptions &o, const ParamRolloutArgs &a,
+                                  hipStream_t stream);
+int launch_rollout_plant_vjp_explicit(int model, int integrator, const DevOptions &o, const ParamRolloutVjpArgs &a,
+                                      hipStream_t stream);
 // plant Euler step x += dt (f(x) + g(x) uact) between two filter calls of the two-stage filters (k_rollout.hip);
 // logs the state / input / rc of the call just made (nullptr to skip) and counts rc < 0 into nfail
 int launch_plant_step(int model, const DevOptions &o, int64_t B, int64_t ld, double dt, double *x, const double *uact,

@@ -700,6 +700,21 @@ struct CartPendulum {
 		safetyHessAt(s, c, x, D2h);
 		dynamicsJacAt(s, c, Df, Dg);
 	}
+	// ... and at a stage state of the plant's step (plant_step.hpp), where no safety set is asked for
+	__device__ static void plantFunctors(const DevOptions &, const double (&x)[NX], double (&f)[NX], double (&g)[NX * NU])
+	{
+		double s, c;
+		trig(x, s, c);
+		dynamicsAt(s, c, x, f, g);
+	}
+	__device__ static void plantAdjointFunctors(const DevOptions &, const double (&x)[NX], double (&f)[NX],
+	                                            double (&g)[NX * NU], double (&Df)[NX * NX], double (&Dg)[NX * NX * NU])
+	{
+		double s, c;
+		trig(x, s, c);
+		dynamicsAt(s, c, x, f, g);
+		dynamicsJacAt(s, c, Df, Dg);
+	}
 };
 
 // ---------------------------------------------------------------------------------------------

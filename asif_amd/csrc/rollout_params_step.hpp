@@ -48,7 +48,7 @@ ASIF_HD void params_step_grads(const StepWorkingSet<M> &ws, double &galpha, doub
 }
 
 // wantP: one of galpha, glb, gub is asked for (the same for every instance of a launch)
-template <class M, class O>
+template <class M, int PLANT = kPlantEuler, class O>
 ASIF_HD void rollout_params_vjp_step(const O &o, const RolloutVjpOpts<M::NU> &e, double dt, const double (&x)[M::NX],
                                      const double (&ut)[M::NU], const double (&k)[M::NU],
                                      const double (&K)[M::NU * M::NX], bool hasK, const double (&v)[M::NU], bool hasV,
@@ -56,7 +56,7 @@ ASIF_HD void rollout_params_vjp_step(const O &o, const RolloutVjpOpts<M::NU> &e,
                                      ParamAdjoint<M> &q)
 {
 	StepWorkingSet<M> ws;
-	rollout_policy_vjp_step<M>(o, e, dt, x, ut, k, K, hasK, v, hasV, rc, gxl, gul, q.p, wantP ? &ws : nullptr);
+	rollout_policy_vjp_step<M, PLANT>(o, e, dt, x, ut, k, K, hasK, v, hasV, rc, gxl, gul, q.p, wantP ? &ws : nullptr);
 	if (wantP) params_step_grads<M>(ws, q.galpha, q.glb, q.gub);
 }
 

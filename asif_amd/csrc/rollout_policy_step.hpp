@@ -45,7 +45,7 @@ struct PolicyAdjoint { // what the policy sweep carries from step to step
 	double gk[M::NU], gK[M::NU * M::NX];
 };
 
-template <class M, class O>
+template <class M, int PLANT = kPlantEuler, class O>
 ASIF_HD void rollout_policy_vjp_step(const O &o, const RolloutVjpOpts<M::NU> &e, double dt, const double (&x)[M::NX],
                                      const double (&ut)[M::NU], const double (&k)[M::NU],
                                      const double (&K)[M::NU * M::NX], bool hasK, const double (&v)[M::NU], bool hasV,
@@ -57,7 +57,7 @@ ASIF_HD void rollout_policy_vjp_step(const O &o, const RolloutVjpOpts<M::NU> &e,
 	policy_udes<NX, NU>(k, K, hasK, x, v, hasV, uDes);
 #pragma unroll
 	for (int j = 0; j < NU; j++) p.s.gudes[j] = 0.0;
-	rollout_vjp_step<M>(o, e, dt, x, ut, uDes, rc, gxl, gul, p.s, out);
+	rollout_vjp_step<M, PLANT>(o, e, dt, x, ut, uDes, rc, gxl, gul, p.s, out);
 #pragma unroll
 	for (int j = 0; j < NU; j++) p.gk[j] += p.s.gudes[j];
 	if (hasK) {

@@ -30,6 +30,7 @@
 #pragma once
 #include <type_traits>
 #include "gi_small.hpp"
+#include "plant_step.hpp"
 
 namespace asif {
 
@@ -106,14 +107,9 @@ ASIF_HD void explicit_step_qp(const double (&h)[NP], const double (&Dh)[NP * NX]
 	qp.ub[NU] = e.relaxLb;
 }
 
-// A model whose functors share work at a state (the cart-driven pendulum: one sine / cosine pair) declares
-// kJointFunctors and supplies stepFunctors (safetySet + dynamics) and adjointFunctors (all four) -- the same values as
-// the four functors one by one, evaluated together.  Every other model is called functor by functor, as before.
-template <class M, class = void>
-struct joint_functors : std::false_type {};
-template <class M>
-struct joint_functors<M, std::enable_if_t<M::kJointFunctors>> : std::true_type {};
-
+// A model with kJointFunctors (plant_step.hpp: joint_functors) supplies stepFunctors (safetySet + dynamics) and
+// adjointFunctors (all four) -- the same values as the four functors one by one, evaluated together.  Every other model is
+// called functor by functor, as before.
 template <class M, class O>
 ASIF_HD void model_step_functors(const O &o, const double (&x)[M::NX], double (&h)[M::NPSS], double (&Dh)[M::NPSS * M::NX],
                                  double (&f)[M::NX], double (&gm)[M::NX * M::NU])
@@ -155,7 +151,8 @@ struct StepWorkingSet { // what a step knows of its filter call, for a caller th
 	double w[M::NU], h[M::NPSS]; // the multiplier of the adjoint system per slot of W; the safety functions at x
 };
 
-template <class M, class O>
+// PLANT: the plant's integrator (plant_step.hpp), Euler unless the caller says otherwise
+template <class M, int PLANT = kPlantEuler, class O>
 ASIF_HD void rollout_vjp_step(const O &o, const RolloutVjpOpts<M::NU> &e, double dt, const double (&x)[M::NX],
                               const double (&ut)[M::NU], const double (&uDes)[M::NU], int rc, const double (&gxl)[M::NX],
                               const double (&gul)[M::NU], RolloutAdjoint<M> &s, StepWorkingSet<M> *out = nullptr)
@@ -165,26 +162,30 @@ ASIF_HD void rollout_vjp_step(const O &o, const RolloutVjpOpts<M::NU> &e, double
 	double h[NP], Dh[NP * NX], f[NX], gm[NX * NU], D2h[NP * NX * NX], Df[NX * NX], Dg[NX * NX * NU];
 	model_adjoint_functors<M>(o, x, h, Dh, f, gm, D2h, Df, Dg);
 
-	// ---- 1. the plant's Euler step backwards
+	// ---- 1. the plant's step backwards (plant_step.hpp)
 	double lamn[NX];
+	if constexpr (PLANT == kPlantEuler) {
 #pragma unroll
-	for (int j = 0; j < NU; j++) {
-		double t = 0.0;
+		for (int j = 0; j < NU; j++) {
+			double t = 0.0;
 #pragma unroll
-		for (int k = 0; k < NX; k++) t += gm[k + j * NX] * s.lam[k];
-		s.mu[j] += gul[j] + dt * t;
-	}
-#pragma unroll
-	for (int m = 0; m < NX; m++) {
-		double t = 0.0;
-#pragma unroll
-		for (int k = 0; k < NX; k++) {
-			double c = Df[k + m * NX];
-#pragma unroll
-			for (int j = 0; j < NU; j++) c += ut[j] * Dg[k + m * NX + j * NX * NX];
-			t += c * s.lam[k];
+			for (int k = 0; k < NX; k++) t += gm[k + j * NX] * s.lam[k];
+			s.mu[j] += gul[j] + dt * t;
 		}
-		lamn[m] = s.lam[m] + dt * t + gxl[m];
+#pragma unroll
+		for (int m = 0; m < NX; m++) {
+			double t = 0.0;
+#pragma unroll
+			for (int k = 0; k < NX; k++) {
+				double c = Df[k + m * NX];
+#pragma unroll
+				for (int j = 0; j < NU; j++) c += ut[j] * Dg[k + m * NX + j * NX * NX];
+				t += c * s.lam[k];
+			}
+			lamn[m] = s.lam[m] + dt * t + gxl[m];
+		}
+	} else {
+		plant_step_adjoint<M, PLANT>(o, dt, x, ut, f, gm, Df, Dg, s.lam, gxl, gul, s.mu, lamn);
 	}
 
 	// ---- 2. the step's QP

@@ -170,8 +170,16 @@ class ExplicitRolloutLayer(torch.nn.Module):
         return ExplicitRolloutFn.apply(self.filter, x0, udes, uact_prev, self.T, self.dt)
 
 
+def _plant(integrator):
+    """"euler" / "rk4" -> capi.PLANT_EULER / capi.PLANT_RK4."""
+    try:
+        return {"euler": capi.PLANT_EULER, "rk4": capi.PLANT_RK4}[integrator]
+    except (KeyError, TypeError):
+        raise ValueError(f'integrator: expected "euler" or "rk4", got {integrator!r}') from None
+
+
 class PolicyRolloutFn(torch.autograd.Function):
-    """xT, uactT, xlog, ulog, rclog, nfail = PolicyRolloutFn.apply(flt, x0, k, K, v, uact_prev, T, dt)
+    """xT, uactT, xlog, ulog, rclog, nfail = PolicyRolloutFn.apply(flt, x0, k, K, v, uact_prev, T, dt[, integrator])
 
     ExplicitRolloutFn with the desired input coming from an affine policy evaluated inside the loop, on the double
     integrator or the cart-driven pendulum (flt: an explicit capi.Filter on one of ROLLOUT_MODELS):
@@ -182,10 +190,15 @@ class PolicyRolloutFn(torch.autograd.Function):
     them; gradients of outputs the caller did not use are handed to it as NULL, and gK / gv are asked for only where K / v
     require a gradient.  A gain shared by the batch is K.expand(-1, B) of a [nu*nx,1] parameter: autograd's own sum over
     the expanded axis turns the per-instance gK into the shared gain's gradient (likewise k and v).
-    The policy's output is not returned: udes_t = k + K xlog[t] + v[t] in torch, and gxlog carries its state part back."""
+    The policy's output is not returned: udes_t = k + K xlog[t] + v[t] in torch, and gxlog carries its state part back.
+    integrator: "euler" (the default: the launches above) or "rk4", the plant stepped by a fourth-order Runge-Kutta step
+    with u_t held over dt, forward and backward through asif_hip_rollout_plant_batch / _vjp_batch.  Those are the
+    params entries' kernels: under "rk4" this function runs them with alpha = lb = ub = NULL (the handle's values in every
+    lane), which computes what a policy kernel would.  The filter is evaluated at the sample instants only under either."""
 
     @staticmethod
-    def forward(ctx, flt, x0, k, K, v, uact_prev, T, dt):
+    def forward(ctx, flt, x0, k, K, v, uact_prev, T, dt, integrator="euler"):
+        plant = _plant(integrator)
         d = flt.dims
         B = x0.shape[1]
         T = int(T)
@@ -209,8 +222,12 @@ class PolicyRolloutFn(torch.autograd.Function):
         ulog = torch.zeros((T, d.nu, B), dtype=torch.float64, device=x.device)
         rclog = torch.zeros((T, B), dtype=torch.int32, device=x.device)
         if B > 0 and T > 0:
-            flt.rollout_policy(T, float(dt), x, k, uact, relax, nfail, K=K, v=v, xlog=xlog, ulog=ulog, rclog=rclog)
-        ctx.flt, ctx.T, ctx.dt, ctx.hasK, ctx.hasV = flt, T, float(dt), K is not None, v is not None
+            if plant == capi.PLANT_EULER:
+                flt.rollout_policy(T, float(dt), x, k, uact, relax, nfail, K=K, v=v, xlog=xlog, ulog=ulog, rclog=rclog)
+            else:
+                flt.rollout_plant(T, float(dt), plant, x, k, uact, relax, nfail, K=K, v=v, xlog=xlog, ulog=ulog,
+                                  rclog=rclog)
+        ctx.flt, ctx.T, ctx.dt, ctx.hasK, ctx.hasV, ctx.plant = flt, T, float(dt), K is not None, v is not None, plant
         ctx.save_for_backward(xlog, ulog, rclog, k, *(t for t in (K, v) if t is not None))
         ctx.mark_non_differentiable(rclog, nfail)
         ctx.set_materialize_grads(False)
@@ -225,7 +242,7 @@ class PolicyRolloutFn(torch.autograd.Function):
         need = ctx.needs_input_grad[1:6]  # x0, k, K, v, uact_prev
         given = [g for g in (gxT, guactT, gxlog, gulog) if g is not None]
         if not any(need) or not given:  # nothing asked for, or no output was used: nothing to launch
-            return (None,) * 8
+            return (None,) * 9
         d = ctx.flt.dims
         B, T = k.shape[1], ctx.T
         cont = lambda g: None if g is None else g.contiguous()
@@ -236,38 +253,47 @@ class PolicyRolloutFn(torch.autograd.Function):
         gv = torch.empty_like(v) if ctx.hasV and need[3] else None
         if B > 0:
             steps = T > 0  # without a step there is no log, no v and no gv to hand over
-            ctx.flt.rollout_policy_vjp(T, ctx.dt, xlog, ulog, rclog, k, gxT, gx0, gk, guact0,
-                                       torch.empty(B, dtype=torch.int32, device=k.device), K=K, v=v if steps else None,
-                                       guactT=cont(guactT), gxlog=cont(gxlog) if steps else None,
-                                       gulog=cont(gulog) if steps else None, gK=gK, gv=gv if steps else None)
-        return (None, gx0 if need[0] else None, gk if need[1] else None, gK, gv, guact0 if need[4] else None, None, None)
+            euler = ctx.plant == capi.PLANT_EULER
+            vjp = ctx.flt.rollout_policy_vjp if euler else ctx.flt.rollout_plant_vjp
+            vjp(T, ctx.dt, *(() if euler else (ctx.plant,)), xlog, ulog, rclog, k, gxT, gx0, gk, guact0,
+                torch.empty(B, dtype=torch.int32, device=k.device), K=K, v=v if steps else None, guactT=cont(guactT),
+                gxlog=cont(gxlog) if steps else None, gulog=cont(gulog) if steps else None, gK=gK,
+                gv=gv if steps else None)
+        # one entry per forward argument, the optional integrator included (dropped where it was not passed)
+        return (None, gx0 if need[0] else None, gk if need[1] else None, gK, gv, guact0 if need[4] else None, None, None,
+                None)
 
 
 class PolicyRolloutLayer(torch.nn.Module):
     """Owns an explicit capi.Filter and rolls the closed loop out for T steps of dt under udes_t = k + K x_t + v_t:
     xT, uactT, xlog, ulog, rclog, nfail = layer(x0, k, K=None, v=None, uact_prev=None)."""
 
-    def __init__(self, model=capi.MODEL_DOUBLE_INTEGRATOR, options=None, solver=None, device=0, T=1, dt=1e-3):
+    def __init__(self, model=capi.MODEL_DOUBLE_INTEGRATOR, options=None, solver=None, device=0, T=1, dt=1e-3,
+                 integrator="euler"):
         super().__init__()
+        _plant(integrator)
         self.filter = capi.Filter(model, capi.EXPLICIT, options=options, solver=solver, device=device)
-        self.T, self.dt = int(T), float(dt)
+        self.T, self.dt, self.integrator = int(T), float(dt), integrator
 
     def forward(self, x0, k, K=None, v=None, uact_prev=None):
-        return PolicyRolloutFn.apply(self.filter, x0, k, K, v, uact_prev, self.T, self.dt)
+        return PolicyRolloutFn.apply(self.filter, x0, k, K, v, uact_prev, self.T, self.dt, self.integrator)
 
 
 class ParamRolloutFn(torch.autograd.Function):
-    """xT, uactT, xlog, ulog, rclog, nfail = ParamRolloutFn.apply(flt, x0, k, K, v, uact_prev, alpha, lb, ub, T, dt)
+    """xT, uactT, xlog, ulog, rclog, nfail = ParamRolloutFn.apply(flt, x0, k, K, v, uact_prev, alpha, lb, ub, T, dt
+                                                                  [, integrator])
 
     PolicyRolloutFn with the filter's own parameters per instance: alpha [B], the barrier gain of
     Lgh u + alpha h >= -Lfh (options.relaxLb), and the input box lb, ub [nu,B]; None is the handle's value.  Gradients
     flow to x0, k, K, v, uact_prev, alpha, lb and ub.  Forward is one asif_hip_rollout_params_batch launch, backward one
     asif_hip_rollout_params_vjp_batch launch; galpha / glb / gub are asked for only where the tensor requires a gradient.
     A gain shared by the batch is alpha.expand(B) of a one-element parameter: autograd's own sum over the expanded axis
-    turns the per-instance galpha into the shared gain's gradient (likewise lb and ub through expand(-1, B))."""
+    turns the per-instance galpha into the shared gain's gradient (likewise lb and ub through expand(-1, B)).
+    integrator: as PolicyRolloutFn's; "rk4" runs asif_hip_rollout_plant_batch / _vjp_batch."""
 
     @staticmethod
-    def forward(ctx, flt, x0, k, K, v, uact_prev, alpha, lb, ub, T, dt):
+    def forward(ctx, flt, x0, k, K, v, uact_prev, alpha, lb, ub, T, dt, integrator="euler"):
+        plant = _plant(integrator)
         d = flt.dims
         B = x0.shape[1]
         T = int(T)
@@ -297,10 +323,14 @@ class ParamRolloutFn(torch.autograd.Function):
         ulog = torch.zeros((T, d.nu, B), dtype=torch.float64, device=x.device)
         rclog = torch.zeros((T, B), dtype=torch.int32, device=x.device)
         if B > 0 and T > 0:
-            flt.rollout_params(T, float(dt), x, k, uact, relax, nfail, K=K, v=v, alpha=alpha, lb=lb, ub=ub, xlog=xlog,
-                               ulog=ulog, rclog=rclog)
+            if plant == capi.PLANT_EULER:
+                flt.rollout_params(T, float(dt), x, k, uact, relax, nfail, K=K, v=v, alpha=alpha, lb=lb, ub=ub,
+                                   xlog=xlog, ulog=ulog, rclog=rclog)
+            else:
+                flt.rollout_plant(T, float(dt), plant, x, k, uact, relax, nfail, K=K, v=v, alpha=alpha, lb=lb, ub=ub,
+                                  xlog=xlog, ulog=ulog, rclog=rclog)
         opt = (K, v, alpha, lb, ub)
-        ctx.flt, ctx.T, ctx.dt, ctx.has = flt, T, float(dt), tuple(t is not None for t in opt)
+        ctx.flt, ctx.T, ctx.dt, ctx.has, ctx.plant = flt, T, float(dt), tuple(t is not None for t in opt), plant
         ctx.save_for_backward(xlog, ulog, rclog, k, *(t for t in opt if t is not None))
         ctx.mark_non_differentiable(rclog, nfail)
         ctx.set_materialize_grads(False)
@@ -314,7 +344,7 @@ class ParamRolloutFn(torch.autograd.Function):
         need = ctx.needs_input_grad[1:9]  # x0, k, K, v, uact_prev, alpha, lb, ub
         given = [g for g in (gxT, guactT, gxlog, gulog) if g is not None]
         if not any(need) or not given:  # nothing asked for, or no output was used: nothing to launch
-            return (None,) * 11
+            return (None,) * 12
         d = ctx.flt.dims
         B, T = k.shape[1], ctx.T
         cont = lambda g: None if g is None else g.contiguous()
@@ -328,13 +358,15 @@ class ParamRolloutFn(torch.autograd.Function):
         gub = torch.empty_like(ub) if ub is not None and need[7] else None
         if B > 0:
             steps = T > 0  # without a step there is no log, no v and no gv to hand over
-            ctx.flt.rollout_params_vjp(T, ctx.dt, xlog, ulog, rclog, k, gxT, gx0, gk, guact0,
-                                       torch.empty(B, dtype=torch.int32, device=k.device), K=K, v=v if steps else None,
-                                       alpha=alpha, lb=lb, ub=ub, guactT=cont(guactT),
-                                       gxlog=cont(gxlog) if steps else None, gulog=cont(gulog) if steps else None,
-                                       gK=gK, gv=gv if steps else None, galpha=galpha, glb=glb, gub=gub)
+            euler = ctx.plant == capi.PLANT_EULER
+            vjp = ctx.flt.rollout_params_vjp if euler else ctx.flt.rollout_plant_vjp
+            vjp(T, ctx.dt, *(() if euler else (ctx.plant,)), xlog, ulog, rclog, k, gxT, gx0, gk, guact0,
+                torch.empty(B, dtype=torch.int32, device=k.device), K=K, v=v if steps else None, alpha=alpha, lb=lb, ub=ub,
+                guactT=cont(guactT), gxlog=cont(gxlog) if steps else None, gulog=cont(gulog) if steps else None, gK=gK,
+                gv=gv if steps else None, galpha=galpha, glb=glb, gub=gub)
+        # one entry per forward argument, the optional integrator included (dropped where it was not passed)
         return (None, gx0 if need[0] else None, gk if need[1] else None, gK, gv, guact0 if need[4] else None, galpha,
-                glb, gub, None, None)
+                glb, gub, None, None, None)
 
 
 class ParamRolloutLayer(torch.nn.Module):
@@ -342,13 +374,15 @@ class ParamRolloutLayer(torch.nn.Module):
     the barrier gain and the input box per instance:
     xT, uactT, xlog, ulog, rclog, nfail = layer(x0, k, K=None, v=None, uact_prev=None, alpha=None, lb=None, ub=None)."""
 
-    def __init__(self, model=capi.MODEL_DOUBLE_INTEGRATOR, options=None, solver=None, device=0, T=1, dt=1e-3):
+    def __init__(self, model=capi.MODEL_DOUBLE_INTEGRATOR, options=None, solver=None, device=0, T=1, dt=1e-3,
+                 integrator="euler"):
         super().__init__()
+        _plant(integrator)
         self.filter = capi.Filter(model, capi.EXPLICIT, options=options, solver=solver, device=device)
-        self.T, self.dt = int(T), float(dt)
+        self.T, self.dt, self.integrator = int(T), float(dt), integrator
 
     def forward(self, x0, k, K=None, v=None, uact_prev=None, alpha=None, lb=None, ub=None):
-        return ParamRolloutFn.apply(self.filter, x0, k, K, v, uact_prev, alpha, lb, ub, self.T, self.dt)
+        return ParamRolloutFn.apply(self.filter, x0, k, K, v, uact_prev, alpha, lb, ub, self.T, self.dt, self.integrator)
 
 
 class QPSolveFn(torch.autograd.Function):

@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define ASIF_HIP_VERSION 190 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
+#define ASIF_HIP_VERSION 200 /* 110: realizable / robust-data handles, solver.presolve, scaling_iters 0 = default;
                               * 120: ASIF_HIP_IMPLICIT_RB (options grew at the end), asif_hip_set_learning, asif_hip_affine_replay;
                               * 130: solver.adaptive_rho_interval (struct grew at the end), polish == 2 is the dual active-set
                               *      stage of gi_small.hpp;
@@ -63,7 +63,10 @@ extern "C" {
                               * 180: asif_hip_rollout_params_batch / asif_hip_rollout_params_vjp_batch, that rollout and its adjoint
                               *      with the barrier gain and the input box per instance, and their gradients;
                               * 190: ASIF_HIP_MODEL_CART_PENDULUM, a synthetic nonlinear one-input model: explicit handles, the
-                              *      filter's vector-Jacobian product and the four policy / params rollout entries */
+                              *      filter's vector-Jacobian product and the four policy / params rollout entries;
+                              * 200: asif_hip_rollout_plant_batch / asif_hip_rollout_plant_vjp_batch, the params rollout and its
+                              *      adjoint with the plant's integrator as an argument: forward Euler or a fourth-order
+                              *      Runge-Kutta step under the held input, with its exact discrete adjoint */
 
 enum asif_hip_error {
 	ASIF_HIP_OK = 0,
@@ -453,6 +456,44 @@ int asif_hip_rollout_params_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx,
                                       const double *gxT, const double *guactT, const double *gxlog, const double *gulog,
                                       double *gx0, double *gK, double *gk, double *gv, double *galpha, double *glb,
                                       double *gub, double *guact0, int32_t *nskip, void *stream);
+
+/* The plant's step between two filter calls of the plant entries below.  The input u_t is held over the control period dt
+ * (zero-order hold); F(X, u) = f(X) + g(X) u:
+ *   EULER: x_{t+1} = x_t + dt F(x_t, u_t), the step of every other rollout entry;
+ *   RK4:   k1 = F(x_t, u_t), k2 = F(x_t + dt/2 k1, u_t), k3 = F(x_t + dt/2 k2, u_t), k4 = F(x_t + dt k3, u_t),
+ *          x_{t+1} = x_t + dt/6 (k1 + 2 k2 + 2 k3 + k4).
+ * Under either the filter is evaluated once per step, at x_t: the barrier condition is enforced at the sample instants
+ * only, and nothing is claimed about the state between them. */
+#define ASIF_HIP_PLANT_EULER 0
+#define ASIF_HIP_PLANT_RK4   1
+
+/* asif_hip_rollout_params_batch with the plant's integrator as an argument.  integrator = ASIF_HIP_PLANT_EULER runs that
+ * entry's own kernels: every output equals its output bit for bit.  ASIF_HIP_PLANT_RK4: the same loop with the RK4 step
+ * above; xlog / ulog / rclog hold what they hold there (the state each filter call saw, the input applied, its verdict).
+ * Any other integrator: ASIF_HIP_EINVAL.  Everything else -- handles (explicit, on DOUBLE_INTEGRATOR or CART_PENDULUM),
+ * solver modes, the optional K, v, alpha, lb, ub and logs, bad parameter data, B == 0, T == 0, refusals -- as
+ * asif_hip_rollout_params_batch. */
+int asif_hip_rollout_plant_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, int32_t integrator,
+                                 double *x, const double *K, const double *k, const double *v, const double *alpha,
+                                 const double *lb, const double *ub, double *uact, double *relax, int32_t *nfail,
+                                 double *xlog, double *ulog, int32_t *rclog, void *stream);
+
+/* asif_hip_rollout_plant_batch backwards, in one launch: asif_hip_rollout_params_vjp_batch with the plant's part of each
+ * step taken through the integrator the forward pass used.  ASIF_HIP_PLANT_EULER runs that entry's own kernels, bit for
+ * bit.  ASIF_HIP_PLANT_RK4: the stage states X_1 = x_t, X_2, X_3, X_4 are recomputed from the logged (x_t, u_t) -- no
+ * log beyond the forward entry's is read -- and with lambda = dL/dx_{t+1}, J_i = Df(X_i) + sum_j u_t,j Dg_j(X_i):
+ *     kb4 = dt/6 lambda,            kb3 = dt/3 lambda + dt J4' kb4,
+ *     kb2 = dt/3 lambda + dt/2 J3' kb3,   kb1 = dt/6 lambda + dt/2 J2' kb2,
+ *     mu += gulog[t] + sum_i g(X_i)' kb_i,   lambda' = lambda + sum_i J_i' kb_i + gxlog[t]
+ * -- the exact derivative of the discrete step -- followed by the filter's adjoint at x_t, unchanged.  Any other
+ * integrator: ASIF_HIP_EINVAL.  Arguments, optional inputs and outputs, T == 0, B == 0, nskip and refusals as
+ * asif_hip_rollout_params_vjp_batch.  The handle's forward results do not change. */
+int asif_hip_rollout_plant_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, int32_t integrator,
+                                     const double *xlog, const double *ulog, const int32_t *rclog, const double *K,
+                                     const double *k, const double *v, const double *alpha, const double *lb,
+                                     const double *ub, const double *gxT, const double *guactT, const double *gxlog,
+                                     const double *gulog, double *gx0, double *gK, double *gk, double *gv, double *galpha,
+                                     double *glb, double *gub, double *guact0, int32_t *nskip, void *stream);
 
 /* Rows only: A[(nc*nv)][ldx], b[nc][ldx], code[B] (1; TB: 2 trivial rows, -3 backup set unreached). */
 int asif_hip_assemble_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, double *A, double *b,
