@@ -996,6 +996,16 @@ extern "C" int asif_hip_filter_batch_lie(asif_hip_ctx *ctx, int64_t B, int64_t l
 	return run_filter(ctx, a, false, (hipStream_t)stream);
 }
 
+// The adjoint entries repeat the forward pass of the default solver mode (the dual active-set stage) and differentiate
+// the working set it ends with; the other modes reach the optimum by iterating and hold no working set.  presolve_too: a
+// forward pass that runs that stage in front of another mode as well (launch_rollout_explicit_di's choice of the light
+// kernel)
+static bool default_solver_mode(const asif_hip_solver &S, bool presolve_too = false)
+{
+	const bool light = S.polish == 2 || (presolve_too && S.presolve);
+	return light && (S.lanes_per_qp == 0 || S.lanes_per_qp == 1);
+}
+
 extern "C" int asif_hip_filter_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, const double *udes,
                                          const double *lfh, const double *lgh, const double *guact, double *gudes,
                                          double *glfh, double *glgh, double *gx, int32_t *rc, void *stream)
@@ -1005,10 +1015,7 @@ extern "C" int asif_hip_filter_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t l
 	// the model's own Lie derivatives: their gradient has no caller, and dL/dx would need the model's second derivatives
 	if (!lfh && (glfh || glgh || gx)) return ASIF_HIP_EINVAL;
 	if (ctx->variant != ASIF_HIP_EXPLICIT || ctx->rz || ctx->rb) return ASIF_HIP_EUNSUPPORTED;
-	const asif_hip_solver &S = ctx->solver;
-	// the backward pass repeats the forward pass of the default solver mode (the dual active-set stage) and differentiates
-	// the working set it ends with; the other modes reach the optimum by iterating and hold no working set
-	if (S.polish != 2 || (S.lanes_per_qp != 0 && S.lanes_per_qp != 1)) return ASIF_HIP_EUNSUPPORTED;
+	if (!default_solver_mode(ctx->solver)) return ASIF_HIP_EUNSUPPORTED;
 	if (B == 0) return ASIF_HIP_OK;
 	hipError_t e = hipSetDevice(ctx->device);
 	if (e != hipSuccess) return (int)e;
@@ -1071,9 +1078,7 @@ extern "C" int asif_hip_rollout_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t 
 	// the fused forward rollout exists for this model alone
 	if (ctx->variant != ASIF_HIP_EXPLICIT || ctx->rz || ctx->rb || ctx->model != ASIF_HIP_MODEL_DOUBLE_INTEGRATOR)
 		return ASIF_HIP_EUNSUPPORTED;
-	const asif_hip_solver &S = ctx->solver;
-	// as asif_hip_filter_vjp_batch: the sweep repeats each step's solve in the default solver mode
-	if (S.polish != 2 || (S.lanes_per_qp != 0 && S.lanes_per_qp != 1)) return ASIF_HIP_EUNSUPPORTED;
+	if (!default_solver_mode(ctx->solver)) return ASIF_HIP_EUNSUPPORTED; // the sweep repeats each step's solve
 	if (B == 0) return ASIF_HIP_OK;
 	hipError_t e = hipSetDevice(ctx->device);
 	if (e != hipSuccess) return (int)e;
@@ -1081,75 +1086,42 @@ extern "C" int asif_hip_rollout_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t 
 	return launch_rollout_vjp_explicit_di(ctx->dev, a, (hipStream_t)stream);
 }
 
-// the four policy / params entries: the fused path's handle (the double integrator or the cart-driven pendulum), in the
-// solver mode the light kernel implements
+// The six policy / params / plant entries: one forward and one backward body.  A further variant is one more `return`
+// line below plus whatever is new in it.
+// the fused path's handle (a model of with_rollout_model), in the solver mode the light kernel implements
 static int policy_rollout_handle(const asif_hip_ctx *ctx, bool presolve_too)
 {
-	const bool model = ctx->model == ASIF_HIP_MODEL_DOUBLE_INTEGRATOR || ctx->model == ASIF_HIP_MODEL_CART_PENDULUM;
-	if (ctx->variant != ASIF_HIP_EXPLICIT || ctx->rz || ctx->rb || !model) return ASIF_HIP_EUNSUPPORTED;
-	const asif_hip_solver &S = ctx->solver;
-	const bool light = S.polish == 2 || (presolve_too && S.presolve); // launch_rollout_explicit_di's choice
-	if (!light || (S.lanes_per_qp != 0 && S.lanes_per_qp != 1)) return ASIF_HIP_EUNSUPPORTED;
-	return ASIF_HIP_OK;
+	if (ctx->variant != ASIF_HIP_EXPLICIT || ctx->rz || ctx->rb || !is_rollout_model(ctx->model)) return ASIF_HIP_EUNSUPPORTED;
+	return default_solver_mode(ctx->solver, presolve_too) ? ASIF_HIP_OK : ASIF_HIP_EUNSUPPORTED;
 }
 
-extern "C" int asif_hip_rollout_policy_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, double *x,
-                                             const double *K, const double *k, const double *v, double *uact,
-                                             double *relax, int32_t *nfail, double *xlog, double *ulog, int32_t *rclog,
-                                             void *stream)
+// params: the entry has alpha / lb / ub (the PARAMS kernels, also where all three are absent)
+static int policy_rollout_forward(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, int32_t integrator,
+                                  bool params, double *x, const double *K, const double *k, const double *v,
+                                  const double *alpha, const double *lb, const double *ub, double *uact, double *relax,
+                                  int32_t *nfail, double *xlog, double *ulog, int32_t *rclog, void *stream)
 {
 	if (!ctx || B < 0 || ldx < B || T < 0 || (B > 0 && (!x || !k || !uact || !relax || !nfail))) return ASIF_HIP_EINVAL;
-	if (int r = policy_rollout_handle(ctx, true)) return r;
-	if (B == 0 || T == 0) return ASIF_HIP_OK;
-	hipError_t e = hipSetDevice(ctx->device);
-	if (e != hipSuccess) return (int)e;
-	const PolicyRolloutArgs a = {B, ldx, T, dt, x, K, k, v, uact, relax, nfail, xlog, ulog, rclog};
-	return launch_rollout_policy_explicit(ctx->model, ctx->dev, a, (hipStream_t)stream);
-}
-
-extern "C" int asif_hip_rollout_policy_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt,
-                                                 const double *xlog, const double *ulog, const int32_t *rclog,
-                                                 const double *K, const double *k, const double *v, const double *gxT,
-                                                 const double *guactT, const double *gxlog, const double *gulog,
-                                                 double *gx0, double *gK, double *gk, double *gv, double *guact0,
-                                                 int32_t *nskip, void *stream)
-{
-	if (!ctx || B < 0 || ldx < B || T < 0) return ASIF_HIP_EINVAL;
-	if (B > 0 && (!k || !gxT || !gx0 || !gk || !guact0 || !nskip)) return ASIF_HIP_EINVAL;
-	if (B > 0 && T > 0 && (!xlog || !ulog || !rclog)) return ASIF_HIP_EINVAL; // no step, no log to read
-	if ((gK && !K) || (gv && !v)) return ASIF_HIP_EINVAL;                     // a gradient of a term that is not there
-	if (int r = policy_rollout_handle(ctx, false)) return r; // the sweep repeats each step's solve in the default mode
-	if (B == 0) return ASIF_HIP_OK;
-	hipError_t e = hipSetDevice(ctx->device);
-	if (e != hipSuccess) return (int)e;
-	const PolicyRolloutVjpArgs a = {B,   ldx,    T,     dt,    xlog, ulog, rclog, K,  k,      v,
-	                                gxT, guactT, gxlog, gulog, gx0,  gK,   gk,    gv, guact0, nskip};
-	return launch_rollout_policy_vjp_explicit(ctx->model, ctx->dev, a, (hipStream_t)stream);
-}
-
-extern "C" int asif_hip_rollout_params_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, double *x,
-                                             const double *K, const double *k, const double *v, const double *alpha,
-                                             const double *lb, const double *ub, double *uact, double *relax,
-                                             int32_t *nfail, double *xlog, double *ulog, int32_t *rclog, void *stream)
-{
-	if (!ctx || B < 0 || ldx < B || T < 0 || (B > 0 && (!x || !k || !uact || !relax || !nfail))) return ASIF_HIP_EINVAL;
+	if (integrator != ASIF_HIP_PLANT_EULER && integrator != ASIF_HIP_PLANT_RK4) return ASIF_HIP_EINVAL;
 	if (int r = policy_rollout_handle(ctx, true)) return r;
 	if (B == 0 || T == 0) return ASIF_HIP_OK;
 	hipError_t e = hipSetDevice(ctx->device);
 	if (e != hipSuccess) return (int)e;
 	const ParamRolloutArgs a = {{B, ldx, T, dt, x, K, k, v, uact, relax, nfail, xlog, ulog, rclog}, alpha, lb, ub};
-	return launch_rollout_params_explicit(ctx->model, ctx->dev, a, (hipStream_t)stream);
+	return launch_rollout_policy_explicit(ctx->model, integrator, params, ctx->dev, a, (hipStream_t)stream);
 }
 
-extern "C" int asif_hip_rollout_params_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt,
-                                                 const double *xlog, const double *ulog, const int32_t *rclog,
-                                                 const double *K, const double *k, const double *v, const double *alpha,
-                                                 const double *lb, const double *ub, const double *gxT,
-                                                 const double *guactT, const double *gxlog, const double *gulog,
-                                                 double *gx0, double *gK, double *gk, double *gv, double *galpha,
-                                                 double *glb, double *gub, double *guact0, int32_t *nskip, void *stream)
+// T == 0 launches too: the kernel writes the identity
+static int policy_rollout_backward(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, int32_t integrator,
+                                   bool params, const double *xlog, const double *ulog, const int32_t *rclog,
+                                   const double *K, const double *k, const double *v, const double *alpha,
+                                   const double *lb, const double *ub, const double *gxT, const double *guactT,
+                                   const double *gxlog, const double *gulog, double *gx0, double *gK, double *gk,
+                                   double *gv, double *galpha, double *glb, double *gub, double *guact0, int32_t *nskip,
+                                   void *stream)
 {
 	if (!ctx || B < 0 || ldx < B || T < 0) return ASIF_HIP_EINVAL;
+	if (integrator != ASIF_HIP_PLANT_EULER && integrator != ASIF_HIP_PLANT_RK4) return ASIF_HIP_EINVAL;
 	if (B > 0 && (!k || !gxT || !gx0 || !gk || !guact0 || !nskip)) return ASIF_HIP_EINVAL;
 	if (B > 0 && T > 0 && (!xlog || !ulog || !rclog)) return ASIF_HIP_EINVAL; // no step, no log to read
 	if ((gK && !K) || (gv && !v)) return ASIF_HIP_EINVAL;                     // a gradient of a term that is not there
@@ -1161,24 +1133,60 @@ extern "C" int asif_hip_rollout_params_vjp_batch(asif_hip_ctx *ctx, int64_t B, i
 	const ParamRolloutVjpArgs a = {{B,   ldx,    T,     dt,    xlog, ulog, rclog, K,  k,      v,
 	                                gxT, guactT, gxlog, gulog, gx0,  gK,   gk,    gv, guact0, nskip},
 	                               alpha, lb, ub, galpha, glb, gub};
-	return launch_rollout_params_vjp_explicit(ctx->model, ctx->dev, a, (hipStream_t)stream);
+	return launch_rollout_policy_vjp_explicit(ctx->model, integrator, params, ctx->dev, a, (hipStream_t)stream);
 }
 
-// the params entries with the plant's integrator as an argument: the same checks in the same order, then the integrator
+extern "C" int asif_hip_rollout_policy_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, double *x,
+                                             const double *K, const double *k, const double *v, double *uact,
+                                             double *relax, int32_t *nfail, double *xlog, double *ulog, int32_t *rclog,
+                                             void *stream)
+{
+	return policy_rollout_forward(ctx, B, ldx, T, dt, ASIF_HIP_PLANT_EULER, false, x, K, k, v, nullptr, nullptr, nullptr, uact,
+	                              relax, nfail, xlog, ulog, rclog, stream);
+}
+
+extern "C" int asif_hip_rollout_policy_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt,
+                                                 const double *xlog, const double *ulog, const int32_t *rclog,
+                                                 const double *K, const double *k, const double *v, const double *gxT,
+                                                 const double *guactT, const double *gxlog, const double *gulog,
+                                                 double *gx0, double *gK, double *gk, double *gv, double *guact0,
+                                                 int32_t *nskip, void *stream)
+{
+	return policy_rollout_backward(ctx, B, ldx, T, dt, ASIF_HIP_PLANT_EULER, false, xlog, ulog, rclog, K, k, v, nullptr,
+	                               nullptr, nullptr, gxT, guactT, gxlog, gulog, gx0, gK, gk, gv, nullptr, nullptr, nullptr,
+	                               guact0, nskip, stream);
+}
+
+extern "C" int asif_hip_rollout_params_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt, double *x,
+                                             const double *K, const double *k, const double *v, const double *alpha,
+                                             const double *lb, const double *ub, double *uact, double *relax,
+                                             int32_t *nfail, double *xlog, double *ulog, int32_t *rclog, void *stream)
+{
+	return policy_rollout_forward(ctx, B, ldx, T, dt, ASIF_HIP_PLANT_EULER, true, x, K, k, v, alpha, lb, ub, uact, relax,
+	                              nfail, xlog, ulog, rclog, stream);
+}
+
+extern "C" int asif_hip_rollout_params_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt,
+                                                 const double *xlog, const double *ulog, const int32_t *rclog,
+                                                 const double *K, const double *k, const double *v, const double *alpha,
+                                                 const double *lb, const double *ub, const double *gxT,
+                                                 const double *guactT, const double *gxlog, const double *gulog,
+                                                 double *gx0, double *gK, double *gk, double *gv, double *galpha,
+                                                 double *glb, double *gub, double *guact0, int32_t *nskip, void *stream)
+{
+	return policy_rollout_backward(ctx, B, ldx, T, dt, ASIF_HIP_PLANT_EULER, true, xlog, ulog, rclog, K, k, v, alpha, lb, ub,
+	                               gxT, guactT, gxlog, gulog, gx0, gK, gk, gv, galpha, glb, gub, guact0, nskip, stream);
+}
+
+// the params entries with the plant's integrator as an argument
 extern "C" int asif_hip_rollout_plant_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt,
                                             int32_t integrator, double *x, const double *K, const double *k,
                                             const double *v, const double *alpha, const double *lb, const double *ub,
                                             double *uact, double *relax, int32_t *nfail, double *xlog, double *ulog,
                                             int32_t *rclog, void *stream)
 {
-	if (!ctx || B < 0 || ldx < B || T < 0 || (B > 0 && (!x || !k || !uact || !relax || !nfail))) return ASIF_HIP_EINVAL;
-	if (integrator != ASIF_HIP_PLANT_EULER && integrator != ASIF_HIP_PLANT_RK4) return ASIF_HIP_EINVAL;
-	if (int r = policy_rollout_handle(ctx, true)) return r;
-	if (B == 0 || T == 0) return ASIF_HIP_OK;
-	hipError_t e = hipSetDevice(ctx->device);
-	if (e != hipSuccess) return (int)e;
-	const ParamRolloutArgs a = {{B, ldx, T, dt, x, K, k, v, uact, relax, nfail, xlog, ulog, rclog}, alpha, lb, ub};
-	return launch_rollout_plant_explicit(ctx->model, integrator, ctx->dev, a, (hipStream_t)stream);
+	return policy_rollout_forward(ctx, B, ldx, T, dt, integrator, true, x, K, k, v, alpha, lb, ub, uact, relax, nfail, xlog,
+	                              ulog, rclog, stream);
 }
 
 extern "C" int asif_hip_rollout_plant_vjp_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, int32_t T, double dt,
@@ -1190,20 +1198,8 @@ extern "C" int asif_hip_rollout_plant_vjp_batch(asif_hip_ctx *ctx, int64_t B, in
                                                 double *galpha, double *glb, double *gub, double *guact0, int32_t *nskip,
                                                 void *stream)
 {
-	if (!ctx || B < 0 || ldx < B || T < 0) return ASIF_HIP_EINVAL;
-	if (integrator != ASIF_HIP_PLANT_EULER && integrator != ASIF_HIP_PLANT_RK4) return ASIF_HIP_EINVAL;
-	if (B > 0 && (!k || !gxT || !gx0 || !gk || !guact0 || !nskip)) return ASIF_HIP_EINVAL;
-	if (B > 0 && T > 0 && (!xlog || !ulog || !rclog)) return ASIF_HIP_EINVAL; // no step, no log to read
-	if ((gK && !K) || (gv && !v)) return ASIF_HIP_EINVAL;                     // a gradient of a term that is not there
-	if ((galpha && !alpha) || (glb && !lb) || (gub && !ub)) return ASIF_HIP_EINVAL; // ... or of a parameter not given
-	if (int r = policy_rollout_handle(ctx, false)) return r; // the sweep repeats each step's solve in the default mode
-	if (B == 0) return ASIF_HIP_OK;
-	hipError_t e = hipSetDevice(ctx->device);
-	if (e != hipSuccess) return (int)e;
-	const ParamRolloutVjpArgs a = {{B,   ldx,    T,     dt,    xlog, ulog, rclog, K,  k,      v,
-	                                gxT, guactT, gxlog, gulog, gx0,  gK,   gk,    gv, guact0, nskip},
-	                               alpha, lb, ub, galpha, glb, gub};
-	return launch_rollout_plant_vjp_explicit(ctx->model, integrator, ctx->dev, a, (hipStream_t)stream);
+	return policy_rollout_backward(ctx, B, ldx, T, dt, integrator, true, xlog, ulog, rclog, K, k, v, alpha, lb, ub, gxT,
+	                               guactT, gxlog, gulog, gx0, gK, gk, gv, galpha, glb, gub, guact0, nskip, stream);
 }
 
 extern "C" int asif_hip_assemble_batch(asif_hip_ctx *ctx, int64_t B, int64_t ldx, const double *x, double *A,

@@ -24,63 +24,37 @@
 // and LAUNCH on top of that: 8 bytes read per parameter given, 8 written per parameter gradient asked for.
 // SoA, every load and store a coalesced line; no LDS, no scratch, no register array indexed by a run-time value.  Lanes
 // beyond B repeat instance B-1 for the solver's votes and never store.
-// Models: DoubleIntegrator and CartPendulum (one input, functors that do not read DevOptions); the launchers at the end
-// dispatch on the handle's model.  A model with kJointFunctors (CartPendulum: one sine / cosine pair per step) is called
-// through its joint forms, model_step_functors / model_adjoint_functors of rollout_vjp_step.hpp.
-// The kernel templates themselves are in rollout_policy_kernels.hpp (k_rollout_plant.hip instantiates them a second time,
-// with the plant stepped by RK4); this file instantiates them for the models as they are and holds the four launchers.
+// Models: DoubleIntegrator and CartPendulum (with_rollout_model, launchers.hpp).  A model with kJointFunctors
+// (CartPendulum: one sine / cosine pair per step) is called through its joint forms, model_step_functors /
+// model_adjoint_functors of rollout_vjp_step.hpp.
+// The kernel templates and the two launch templates (grid, HASV, WANTP) are in rollout_policy_kernels.hpp.  This file
+// instantiates them for the models as they are, PARAMS false and true, and holds the two launchers every entry goes
+// through: the policy entries (params = false), the params entries and the plant entries under Euler (params = true) run
+// this file's kernels; the plant entries under RK4 are handed to k_rollout_plant.hip, which instantiates the templates a
+// second time on WithRk4<model>.
 #include "rollout_policy_kernels.hpp"
 
 namespace asif {
 
-template <class M, bool PARAMS>
-static int launch_forward(const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream)
+int launch_rollout_policy_explicit(int model, int integrator, bool params, const DevOptions &o, const ParamRolloutArgs &a,
+                                   hipStream_t stream)
 {
-	if (a.p.B <= 0 || a.p.T <= 0) return 0;
-	const dim3 grid(grid_for(a.p.B, 1, 256)), block(256);
-	const RolloutVjpOpts<M::NU> e = rollout_class_opts<M>(o);
-	if (a.p.v) hipLaunchKernelGGL((rollout_policy_kernel<M, true, PARAMS>), grid, block, 0, stream, e, a);
-	else hipLaunchKernelGGL((rollout_policy_kernel<M, false, PARAMS>), grid, block, 0, stream, e, a);
-	return (int)hipGetLastError();
-}
-
-template <class M, bool PARAMS, bool WANTP>
-static int launch_backward(const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream)
-{
-	if (a.p.B <= 0) return 0;
-	hipLaunchKernelGGL((rollout_policy_vjp_kernel<M, PARAMS, WANTP>), dim3(grid_for(a.p.B, 1, 256)), dim3(256), 0, stream,
-	                   rollout_class_opts<M>(o), a);
-	return (int)hipGetLastError();
-}
-
-int launch_rollout_policy_explicit(int model, const DevOptions &o, const PolicyRolloutArgs &a, hipStream_t stream)
-{
+	if (integrator == ASIF_HIP_PLANT_RK4) return params ? launch_rk4(model, o, a, stream) : ASIF_HIP_EUNSUPPORTED;
+	if (integrator != ASIF_HIP_PLANT_EULER) return ASIF_HIP_EINVAL;
 	return with_rollout_model(model, [&](auto m) {
-		return launch_forward<decltype(m), false>(o, ParamRolloutArgs{a, nullptr, nullptr, nullptr}, stream);
+		using M = decltype(m);
+		return params ? launch_forward<M, true>(o, a, stream) : launch_forward<M, false>(o, a, stream);
 	});
 }
 
-// T == 0 runs the kernel too: it writes the identity (gx0 = gxT, guact0 = guactT or 0, gk = 0, gK = 0, nskip = 0, no gv)
-int launch_rollout_policy_vjp_explicit(int model, const DevOptions &o, const PolicyRolloutVjpArgs &a, hipStream_t stream)
+int launch_rollout_policy_vjp_explicit(int model, int integrator, bool params, const DevOptions &o,
+                                       const ParamRolloutVjpArgs &a, hipStream_t stream)
 {
+	if (integrator == ASIF_HIP_PLANT_RK4) return params ? launch_rk4(model, o, a, stream) : ASIF_HIP_EUNSUPPORTED;
+	if (integrator != ASIF_HIP_PLANT_EULER) return ASIF_HIP_EINVAL;
 	return with_rollout_model(model, [&](auto m) {
-		return launch_backward<decltype(m), false, false>(
-			o, ParamRolloutVjpArgs{a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, stream);
-	});
-}
-
-// the PARAMS kernels also where all three parameters are absent
-int launch_rollout_params_explicit(int model, const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream)
-{
-	return with_rollout_model(model, [&](auto m) { return launch_forward<decltype(m), true>(o, a, stream); });
-}
-
-// T == 0: the identity of launch_rollout_policy_vjp_explicit, and galpha = glb = gub = 0
-int launch_rollout_params_vjp_explicit(int model, const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream)
-{
-	return with_rollout_model(model, [&](auto m) {
-		if (a.galpha || a.glb || a.gub) return launch_backward<decltype(m), true, true>(o, a, stream);
-		return launch_backward<decltype(m), true, false>(o, a, stream);
+		using M = decltype(m);
+		return params ? launch_backward<M, true>(o, a, stream) : launch_backward<M, false>(o, a, stream);
 	});
 }
 

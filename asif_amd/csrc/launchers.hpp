@@ -86,8 +86,8 @@ struct RolloutVjpArgs {
 	int32_t *nskip;               // [B] steps with rclog == 1 that the kernel's own solve did not decide
 };
 int launch_rollout_vjp_explicit_di(const DevOptions &o, const RolloutVjpArgs &a, hipStream_t stream);
-// the fused explicit rollout under an affine policy uDes_t = k + K x_t + v_t and its adjoint (k_rollout_policy.hip);
-// model = DoubleIntegrator / CartPendulum (the four launchers dispatch on it; any other: ASIF_HIP_EUNSUPPORTED)
+// the fused explicit rollout under an affine policy uDes_t = k + K x_t + v_t and its adjoint, optionally with the barrier gain
+// and the input box per instance and with the plant's integrator chosen by the caller (rollout_policy_kernels.hpp)
 struct PolicyRolloutArgs {
 	int64_t B, ld;
 	int T;
@@ -99,7 +99,6 @@ struct PolicyRolloutArgs {
 	double *xlog, *ulog;       // as RolloutArgs, each may be nullptr
 	int32_t *rclog;
 };
-int launch_rollout_policy_explicit(int model, const DevOptions &o, const PolicyRolloutArgs &a, hipStream_t stream);
 struct PolicyRolloutVjpArgs {
 	int64_t B, ld;
 	int T;
@@ -111,25 +110,39 @@ struct PolicyRolloutVjpArgs {
 	double *gx0, *gK, *gk, *gv, *guact0; // [nx][ld]; [nu*nx][ld] or nullptr; [nu][ld]; [T][nu][ld] or nullptr; [nu][ld]
 	int32_t *nskip;                      // [B]
 };
-int launch_rollout_policy_vjp_explicit(int model, const DevOptions &o, const PolicyRolloutVjpArgs &a, hipStream_t stream);
-// the same rollout with the barrier gain and the input box per instance, and its adjoint (k_rollout_policy.hip, PARAMS)
 struct ParamRolloutArgs {
 	PolicyRolloutArgs p;
 	const double *alpha, *lb, *ub; // [B], [nu][ld], [nu][ld]; each may be nullptr: the handle's value
 };
-int launch_rollout_params_explicit(int model, const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream);
 struct ParamRolloutVjpArgs {
 	PolicyRolloutVjpArgs p;
 	const double *alpha, *lb, *ub; // as ParamRolloutArgs
 	double *galpha, *glb, *gub;    // [B], [nu][ld], [nu][ld]; each may be nullptr: not wanted
 };
-int launch_rollout_params_vjp_explicit(int model, const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream);
-// the params rollout and its adjoint with the plant's integrator as an argument (k_rollout_plant.hip): ASIF_HIP_PLANT_EULER
-// is the two launchers above, ASIF_HIP_PLANT_RK4 the RK4 instantiations; any other integrator: ASIF_HIP_EINVAL
-int launch_rollout_plant_explicit(int model, int integrator, const DevOptions &o, const ParamRolloutArgs &a,
-                                  hipStream_t stream);
-int launch_rollout_plant_vjp_explicit(int model, int integrator, const DevOptions &o, const ParamRolloutVjpArgs &a,
-                                      hipStream_t stream);
+// the models these rollouts are compiled for: one input, functors that do not read DevOptions.  f is called with a value
+// of the model's type; any other model: ASIF_HIP_EUNSUPPORTED
+template <class F>
+int with_rollout_model(int model, F &&f)
+{
+	switch (model) {
+	case ASIF_HIP_MODEL_DOUBLE_INTEGRATOR: return f(DoubleIntegrator{});
+	case ASIF_HIP_MODEL_CART_PENDULUM: return f(CartPendulum{});
+	default: return ASIF_HIP_EUNSUPPORTED;
+	}
+}
+inline bool is_rollout_model(int model)
+{
+	return with_rollout_model(model, [](auto) { return 0; }) == 0;
+}
+// One forward and one backward launcher for every entry (k_rollout_policy.hip).  params: the PARAMS kernels, which look at
+// alpha / lb / ub (also where all three are absent); without it the three and their gradients must be nullptr.
+// integrator: ASIF_HIP_PLANT_EULER, or ASIF_HIP_PLANT_RK4 (with params only: k_rollout_plant.hip's instantiations); any
+// other: ASIF_HIP_EINVAL.  The backward launcher runs the kernel with T == 0 too: it writes the identity (gx0 = gxT,
+// guact0 = guactT or 0, every other gradient asked for 0, nskip = 0, no gv)
+int launch_rollout_policy_explicit(int model, int integrator, bool params, const DevOptions &o, const ParamRolloutArgs &a,
+                                   hipStream_t stream);
+int launch_rollout_policy_vjp_explicit(int model, int integrator, bool params, const DevOptions &o,
+                                       const ParamRolloutVjpArgs &a, hipStream_t stream);
 // plant Euler step x += dt (f(x) + g(x) uact) between two filter calls of the two-stage filters (k_rollout.hip);
 // logs the state / input / rc of the call just made (nullptr to skip) and counts rc < 0 into nfail
 int launch_plant_step(int model, const DevOptions &o, int64_t B, int64_t ld, double dt, double *x, const double *uact,

@@ -1,8 +1,8 @@
 // rollout_policy_kernels.hpp -- the kernels of the fused rollout under an affine policy and of its adjoint, one instance
-// per lane: what k_rollout_policy.hip describes.  Two translation units instantiate them: k_rollout_policy.hip for the
-// models as they are (Euler: the policy and the params entries), k_rollout_plant.hip for WithRk4<model> (the plant
-// entries).  The plant's integrator rides on the model type so that the kernels the policy and the params entries run keep
-// their names and their code.
+// per lane, and their launches: what k_rollout_policy.hip describes.  Two translation units instantiate them:
+// k_rollout_policy.hip for the models as they are (Euler: the policy and the params entries, the plant entries under
+// Euler), k_rollout_plant.hip for WithRk4<model> (the plant entries under RK4).  The plant's integrator rides on the model
+// type so that the kernels the policy and the params entries run keep their names and their code.
 #pragma once
 #include <cstdint>
 #include "launchers.hpp"
@@ -248,16 +248,39 @@ __global__ __launch_bounds__(256) void rollout_policy_vjp_kernel(RolloutVjpOpts<
 	a.nskip[i] = p.s.nskip;
 }
 
-// the models these rollouts are compiled for: one input, functors that do not read DevOptions.  f is called with a value
-// of the model's type
-template <class F>
-static int with_rollout_model(int model, F &&f)
+// The launches, written once for both translation units: one instance per lane, 256-thread workgroups; HASV from a.p.v.
+// Without an instance or a step the forward pass has nothing to do.
+template <class M, bool PARAMS>
+static int launch_forward(const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream)
 {
-	switch (model) {
-	case ASIF_HIP_MODEL_DOUBLE_INTEGRATOR: return f(DoubleIntegrator{});
-	case ASIF_HIP_MODEL_CART_PENDULUM: return f(CartPendulum{});
-	default: return ASIF_HIP_EUNSUPPORTED;
-	}
+	if (a.p.B <= 0 || a.p.T <= 0) return 0;
+	const dim3 grid(grid_for(a.p.B, 1, 256)), block(256);
+	const RolloutVjpOpts<M::NU> e = rollout_class_opts<M>(o);
+	if (a.p.v) hipLaunchKernelGGL((rollout_policy_kernel<M, true, PARAMS>), grid, block, 0, stream, e, a);
+	else hipLaunchKernelGGL((rollout_policy_kernel<M, false, PARAMS>), grid, block, 0, stream, e, a);
+	return (int)hipGetLastError();
 }
+
+// T == 0 runs the kernel too (the identity).  WANTP where one of the three parameter gradients is asked for: without it
+// the step hands nothing out and the loop is the policy entry's
+template <class M, bool PARAMS>
+static int launch_backward(const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream)
+{
+	if (a.p.B <= 0) return 0;
+	const dim3 grid(grid_for(a.p.B, 1, 256)), block(256);
+	const RolloutVjpOpts<M::NU> e = rollout_class_opts<M>(o);
+	if constexpr (PARAMS) {
+		if (a.galpha || a.glb || a.gub) hipLaunchKernelGGL((rollout_policy_vjp_kernel<M, true, true>), grid, block, 0, stream, e, a);
+		else hipLaunchKernelGGL((rollout_policy_vjp_kernel<M, true, false>), grid, block, 0, stream, e, a);
+	} else {
+		hipLaunchKernelGGL((rollout_policy_vjp_kernel<M, false, false>), grid, block, 0, stream, e, a);
+	}
+	return (int)hipGetLastError();
+}
+
+// launch_forward / launch_backward on WithRk4<model> with PARAMS: defined in k_rollout_plant.hip, where alone the RK4
+// code is compiled, and called by the two launchers in k_rollout_policy.hip
+int launch_rk4(int model, const DevOptions &o, const ParamRolloutArgs &a, hipStream_t stream);
+int launch_rk4(int model, const DevOptions &o, const ParamRolloutVjpArgs &a, hipStream_t stream);
 
 } // namespace asif

@@ -98,6 +98,18 @@ class ExplicitSafetyLayer(torch.nn.Module):
         return ExplicitFilterFn.apply(self.filter, x, udes, lfh, lgh, uact_prev)
 
 
+def _rollout_buffers(d, B, T, uact_prev, device):
+    """What a T-step rollout writes: uact (a copy of uact_prev, or zeros), relax, nfail and the logs xlog, ulog, rclog."""
+    uact = (_soa(uact_prev, d.nu, B, "uact_prev").clone() if uact_prev is not None
+            else torch.zeros((d.nu, B), dtype=torch.float64, device=device))
+    relax = torch.zeros((d.nrelax, B), dtype=torch.float64, device=device)
+    nfail = torch.zeros(B, dtype=torch.int32, device=device)
+    xlog = torch.zeros((T, d.nx, B), dtype=torch.float64, device=device)
+    ulog = torch.zeros((T, d.nu, B), dtype=torch.float64, device=device)
+    rclog = torch.zeros((T, B), dtype=torch.int32, device=device)
+    return uact, relax, nfail, xlog, ulog, rclog
+
+
 class ExplicitRolloutFn(torch.autograd.Function):
     """xT, uactT, xlog, ulog, rclog, nfail = ExplicitRolloutFn.apply(flt, x0, udes, uact_prev, T, dt)
 
@@ -122,13 +134,7 @@ class ExplicitRolloutFn(torch.autograd.Function):
                              "integrator only; on the cart-driven pendulum use PolicyRolloutFn with K = v = None")
         x = _soa(x0, d.nx, B, "x0").clone()
         udes = _soa(udes, d.nu, B, "udes")
-        uact = (_soa(uact_prev, d.nu, B, "uact_prev").clone() if uact_prev is not None
-                else torch.zeros((d.nu, B), dtype=torch.float64, device=x.device))
-        relax = torch.zeros((d.nrelax, B), dtype=torch.float64, device=x.device)
-        nfail = torch.zeros(B, dtype=torch.int32, device=x.device)
-        xlog = torch.zeros((T, d.nx, B), dtype=torch.float64, device=x.device)
-        ulog = torch.zeros((T, d.nu, B), dtype=torch.float64, device=x.device)
-        rclog = torch.zeros((T, B), dtype=torch.int32, device=x.device)
+        uact, relax, nfail, xlog, ulog, rclog = _rollout_buffers(d, B, T, uact_prev, x.device)
         if B > 0 and T > 0:
             flt.rollout(T, float(dt), x, udes, uact, relax, nfail, xlog, ulog, rclog)
         ctx.flt, ctx.T, ctx.dt = flt, T, float(dt)
@@ -178,6 +184,86 @@ def _plant(integrator):
         raise ValueError(f'integrator: expected "euler" or "rk4", got {integrator!r}') from None
 
 
+def _policy_rollout_entry(plant, has_params):
+    """The capi.Filter method of the forward pass; its adjoint is the same name with _vjp."""
+    if plant != capi.PLANT_EULER:
+        return "rollout_plant"
+    return "rollout_params" if has_params else "rollout_policy"
+
+
+def _policy_rollout_forward(ctx, flt, x0, k, K, v, uact_prev, params, T, dt, integrator):
+    """PolicyRolloutFn.forward (params None) and ParamRolloutFn.forward (params = (alpha, lb, ub), each may be None)."""
+    plant = _plant(integrator)
+    d = flt.dims
+    B = x0.shape[1]
+    T = int(T)
+    if T < 0:
+        raise ValueError(f"T: expected a non-negative step count, got {T}")
+    if flt.model not in ROLLOUT_MODELS or flt.variant != capi.EXPLICIT:
+        raise ValueError("the differentiable rollout under a policy exists for the explicit filter on the double "
+                         "integrator and on the cart-driven pendulum")
+    x = _soa(x0, d.nx, B, "x0").clone()
+    k = _soa(k, d.nu, B, "k")
+    K = _soa(K, d.nu * d.nx, B, "K") if K is not None else None
+    if v is not None:
+        if v.dim() != 3 or v.shape[0] != T:
+            raise ValueError(f"v: expected shape ({T}, {d.nu}, {B}), got {tuple(v.shape)}")
+        v = _soa(v.reshape(T * d.nu, B), T * d.nu, B, "v").reshape(T, d.nu, B)
+    opt = dict(K=K, v=v)
+    if params is not None:
+        alpha, lb, ub = params
+        if alpha is not None:
+            if alpha.dim() != 1:
+                raise ValueError(f"alpha: expected shape ({B},), got {tuple(alpha.shape)}")
+            alpha = _soa(alpha[None, :], 1, B, "alpha")[0]
+        lb = _soa(lb, d.nu, B, "lb") if lb is not None else None
+        ub = _soa(ub, d.nu, B, "ub") if ub is not None else None
+        opt.update(alpha=alpha, lb=lb, ub=ub)
+    uact, relax, nfail, xlog, ulog, rclog = _rollout_buffers(d, B, T, uact_prev, x.device)
+    if B > 0 and T > 0:
+        getattr(flt, _policy_rollout_entry(plant, params is not None))(
+            T, float(dt), *(() if plant == capi.PLANT_EULER else (plant,)), x, k, uact, relax, nfail, **opt, xlog=xlog,
+            ulog=ulog, rclog=rclog)
+    ctx.flt, ctx.T, ctx.dt, ctx.plant, ctx.params = flt, T, float(dt), plant, params is not None
+    ctx.opt = tuple(name for name, t in opt.items() if t is not None)
+    ctx.save_for_backward(xlog, ulog, rclog, k, *(opt[name] for name in ctx.opt))
+    ctx.mark_non_differentiable(rclog, nfail)
+    ctx.set_materialize_grads(False)
+    return x, uact, xlog, ulog, rclog, nfail
+
+
+def _policy_rollout_backward(ctx, gxT, guactT, gxlog, gulog):
+    """The backward pass of both: one gradient per forward argument, the optional integrator included (autograd drops it
+    where it was not passed) -- 9 without the parameters, 12 with them."""
+    xlog, ulog, rclog, k = ctx.saved_tensors[:4]
+    opt = dict(zip(ctx.opt, ctx.saved_tensors[4:]))
+    K, v = opt.get("K"), opt.get("v")
+    pnames = ("alpha", "lb", "ub") if ctx.params else ()
+    need = ctx.needs_input_grad[1:6 + len(pnames)]  # x0, k, K, v, uact_prev[, alpha, lb, ub]
+    given = [g for g in (gxT, guactT, gxlog, gulog) if g is not None]
+    if not any(need) or not given:  # nothing asked for, or no output was used: nothing to launch
+        return (None,) * (9 + len(pnames))
+    d = ctx.flt.dims
+    B, T = k.shape[1], ctx.T
+    cont = lambda g: None if g is None else g.contiguous()
+    gxT = cont(gxT) if gxT is not None else torch.zeros((d.nx, B), dtype=torch.float64, device=k.device)
+    gx0 = torch.empty((d.nx, B), dtype=torch.float64, device=k.device)
+    gk, guact0 = torch.empty_like(k), torch.empty_like(k)
+    gK = torch.empty_like(K) if K is not None and need[2] else None
+    gv = torch.empty_like(v) if v is not None and need[3] else None
+    # galpha / glb / gub: only for a parameter that was given and requires a gradient
+    pgrad = {"g" + name: torch.empty_like(opt[name]) if name in opt and nd else None for name, nd in zip(pnames, need[5:])}
+    if B > 0:
+        steps = T > 0  # without a step there is no log, no v and no gv to hand over
+        getattr(ctx.flt, _policy_rollout_entry(ctx.plant, ctx.params) + "_vjp")(
+            T, ctx.dt, *(() if ctx.plant == capi.PLANT_EULER else (ctx.plant,)), xlog, ulog, rclog, k, gxT, gx0, gk, guact0,
+            torch.empty(B, dtype=torch.int32, device=k.device), K=K, v=v if steps else None,
+            **{name: opt.get(name) for name in pnames}, guactT=cont(guactT), gxlog=cont(gxlog) if steps else None,
+            gulog=cont(gulog) if steps else None, gK=gK, gv=gv if steps else None, **pgrad)
+    return (None, gx0 if need[0] else None, gk if need[1] else None, gK, gv, guact0 if need[4] else None,
+            *pgrad.values(), None, None, None)
+
+
 class PolicyRolloutFn(torch.autograd.Function):
     """xT, uactT, xlog, ulog, rclog, nfail = PolicyRolloutFn.apply(flt, x0, k, K, v, uact_prev, T, dt[, integrator])
 
@@ -198,85 +284,11 @@ class PolicyRolloutFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flt, x0, k, K, v, uact_prev, T, dt, integrator="euler"):
-        plant = _plant(integrator)
-        d = flt.dims
-        B = x0.shape[1]
-        T = int(T)
-        if T < 0:
-            raise ValueError(f"T: expected a non-negative step count, got {T}")
-        if flt.model not in ROLLOUT_MODELS or flt.variant != capi.EXPLICIT:
-            raise ValueError("the differentiable rollout under a policy exists for the explicit filter on the double "
-                             "integrator and on the cart-driven pendulum")
-        x = _soa(x0, d.nx, B, "x0").clone()
-        k = _soa(k, d.nu, B, "k")
-        K = _soa(K, d.nu * d.nx, B, "K") if K is not None else None
-        if v is not None:
-            if v.dim() != 3 or v.shape[0] != T:
-                raise ValueError(f"v: expected shape ({T}, {d.nu}, {B}), got {tuple(v.shape)}")
-            v = _soa(v.reshape(T * d.nu, B), T * d.nu, B, "v").reshape(T, d.nu, B)
-        uact = (_soa(uact_prev, d.nu, B, "uact_prev").clone() if uact_prev is not None
-                else torch.zeros((d.nu, B), dtype=torch.float64, device=x.device))
-        relax = torch.zeros((d.nrelax, B), dtype=torch.float64, device=x.device)
-        nfail = torch.zeros(B, dtype=torch.int32, device=x.device)
-        xlog = torch.zeros((T, d.nx, B), dtype=torch.float64, device=x.device)
-        ulog = torch.zeros((T, d.nu, B), dtype=torch.float64, device=x.device)
-        rclog = torch.zeros((T, B), dtype=torch.int32, device=x.device)
-        if B > 0 and T > 0:
-            if plant == capi.PLANT_EULER:
-                flt.rollout_policy(T, float(dt), x, k, uact, relax, nfail, K=K, v=v, xlog=xlog, ulog=ulog, rclog=rclog)
-            else:
-                flt.rollout_plant(T, float(dt), plant, x, k, uact, relax, nfail, K=K, v=v, xlog=xlog, ulog=ulog,
-                                  rclog=rclog)
-        ctx.flt, ctx.T, ctx.dt, ctx.hasK, ctx.hasV, ctx.plant = flt, T, float(dt), K is not None, v is not None, plant
-        ctx.save_for_backward(xlog, ulog, rclog, k, *(t for t in (K, v) if t is not None))
-        ctx.mark_non_differentiable(rclog, nfail)
-        ctx.set_materialize_grads(False)
-        return x, uact, xlog, ulog, rclog, nfail
+        return _policy_rollout_forward(ctx, flt, x0, k, K, v, uact_prev, None, T, dt, integrator)
 
     @staticmethod
     def backward(ctx, gxT, guactT, gxlog, gulog, _grclog, _gnfail):
-        xlog, ulog, rclog, k = ctx.saved_tensors[:4]
-        rest = list(ctx.saved_tensors[4:])
-        K = rest.pop(0) if ctx.hasK else None
-        v = rest.pop(0) if ctx.hasV else None
-        need = ctx.needs_input_grad[1:6]  # x0, k, K, v, uact_prev
-        given = [g for g in (gxT, guactT, gxlog, gulog) if g is not None]
-        if not any(need) or not given:  # nothing asked for, or no output was used: nothing to launch
-            return (None,) * 9
-        d = ctx.flt.dims
-        B, T = k.shape[1], ctx.T
-        cont = lambda g: None if g is None else g.contiguous()
-        gxT = cont(gxT) if gxT is not None else torch.zeros((d.nx, B), dtype=torch.float64, device=k.device)
-        gx0 = torch.empty((d.nx, B), dtype=torch.float64, device=k.device)
-        gk, guact0 = torch.empty_like(k), torch.empty_like(k)
-        gK = torch.empty_like(K) if ctx.hasK and need[2] else None
-        gv = torch.empty_like(v) if ctx.hasV and need[3] else None
-        if B > 0:
-            steps = T > 0  # without a step there is no log, no v and no gv to hand over
-            euler = ctx.plant == capi.PLANT_EULER
-            vjp = ctx.flt.rollout_policy_vjp if euler else ctx.flt.rollout_plant_vjp
-            vjp(T, ctx.dt, *(() if euler else (ctx.plant,)), xlog, ulog, rclog, k, gxT, gx0, gk, guact0,
-                torch.empty(B, dtype=torch.int32, device=k.device), K=K, v=v if steps else None, guactT=cont(guactT),
-                gxlog=cont(gxlog) if steps else None, gulog=cont(gulog) if steps else None, gK=gK,
-                gv=gv if steps else None)
-        # one entry per forward argument, the optional integrator included (dropped where it was not passed)
-        return (None, gx0 if need[0] else None, gk if need[1] else None, gK, gv, guact0 if need[4] else None, None, None,
-                None)
-
-
-class PolicyRolloutLayer(torch.nn.Module):
-    """Owns an explicit capi.Filter and rolls the closed loop out for T steps of dt under udes_t = k + K x_t + v_t:
-    xT, uactT, xlog, ulog, rclog, nfail = layer(x0, k, K=None, v=None, uact_prev=None)."""
-
-    def __init__(self, model=capi.MODEL_DOUBLE_INTEGRATOR, options=None, solver=None, device=0, T=1, dt=1e-3,
-                 integrator="euler"):
-        super().__init__()
-        _plant(integrator)
-        self.filter = capi.Filter(model, capi.EXPLICIT, options=options, solver=solver, device=device)
-        self.T, self.dt, self.integrator = int(T), float(dt), integrator
-
-    def forward(self, x0, k, K=None, v=None, uact_prev=None):
-        return PolicyRolloutFn.apply(self.filter, x0, k, K, v, uact_prev, self.T, self.dt, self.integrator)
+        return _policy_rollout_backward(ctx, gxT, guactT, gxlog, gulog)
 
 
 class ParamRolloutFn(torch.autograd.Function):
@@ -293,86 +305,15 @@ class ParamRolloutFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flt, x0, k, K, v, uact_prev, alpha, lb, ub, T, dt, integrator="euler"):
-        plant = _plant(integrator)
-        d = flt.dims
-        B = x0.shape[1]
-        T = int(T)
-        if T < 0:
-            raise ValueError(f"T: expected a non-negative step count, got {T}")
-        if flt.model not in ROLLOUT_MODELS or flt.variant != capi.EXPLICIT:
-            raise ValueError("the differentiable rollout under a policy exists for the explicit filter on the double "
-                             "integrator and on the cart-driven pendulum")
-        x = _soa(x0, d.nx, B, "x0").clone()
-        k = _soa(k, d.nu, B, "k")
-        K = _soa(K, d.nu * d.nx, B, "K") if K is not None else None
-        if v is not None:
-            if v.dim() != 3 or v.shape[0] != T:
-                raise ValueError(f"v: expected shape ({T}, {d.nu}, {B}), got {tuple(v.shape)}")
-            v = _soa(v.reshape(T * d.nu, B), T * d.nu, B, "v").reshape(T, d.nu, B)
-        if alpha is not None:
-            if alpha.dim() != 1:
-                raise ValueError(f"alpha: expected shape ({B},), got {tuple(alpha.shape)}")
-            alpha = _soa(alpha[None, :], 1, B, "alpha")[0]
-        lb = _soa(lb, d.nu, B, "lb") if lb is not None else None
-        ub = _soa(ub, d.nu, B, "ub") if ub is not None else None
-        uact = (_soa(uact_prev, d.nu, B, "uact_prev").clone() if uact_prev is not None
-                else torch.zeros((d.nu, B), dtype=torch.float64, device=x.device))
-        relax = torch.zeros((d.nrelax, B), dtype=torch.float64, device=x.device)
-        nfail = torch.zeros(B, dtype=torch.int32, device=x.device)
-        xlog = torch.zeros((T, d.nx, B), dtype=torch.float64, device=x.device)
-        ulog = torch.zeros((T, d.nu, B), dtype=torch.float64, device=x.device)
-        rclog = torch.zeros((T, B), dtype=torch.int32, device=x.device)
-        if B > 0 and T > 0:
-            if plant == capi.PLANT_EULER:
-                flt.rollout_params(T, float(dt), x, k, uact, relax, nfail, K=K, v=v, alpha=alpha, lb=lb, ub=ub,
-                                   xlog=xlog, ulog=ulog, rclog=rclog)
-            else:
-                flt.rollout_plant(T, float(dt), plant, x, k, uact, relax, nfail, K=K, v=v, alpha=alpha, lb=lb, ub=ub,
-                                  xlog=xlog, ulog=ulog, rclog=rclog)
-        opt = (K, v, alpha, lb, ub)
-        ctx.flt, ctx.T, ctx.dt, ctx.has, ctx.plant = flt, T, float(dt), tuple(t is not None for t in opt), plant
-        ctx.save_for_backward(xlog, ulog, rclog, k, *(t for t in opt if t is not None))
-        ctx.mark_non_differentiable(rclog, nfail)
-        ctx.set_materialize_grads(False)
-        return x, uact, xlog, ulog, rclog, nfail
+        return _policy_rollout_forward(ctx, flt, x0, k, K, v, uact_prev, (alpha, lb, ub), T, dt, integrator)
 
     @staticmethod
     def backward(ctx, gxT, guactT, gxlog, gulog, _grclog, _gnfail):
-        xlog, ulog, rclog, k = ctx.saved_tensors[:4]
-        rest = list(ctx.saved_tensors[4:])
-        K, v, alpha, lb, ub = (rest.pop(0) if has else None for has in ctx.has)
-        need = ctx.needs_input_grad[1:9]  # x0, k, K, v, uact_prev, alpha, lb, ub
-        given = [g for g in (gxT, guactT, gxlog, gulog) if g is not None]
-        if not any(need) or not given:  # nothing asked for, or no output was used: nothing to launch
-            return (None,) * 12
-        d = ctx.flt.dims
-        B, T = k.shape[1], ctx.T
-        cont = lambda g: None if g is None else g.contiguous()
-        gxT = cont(gxT) if gxT is not None else torch.zeros((d.nx, B), dtype=torch.float64, device=k.device)
-        gx0 = torch.empty((d.nx, B), dtype=torch.float64, device=k.device)
-        gk, guact0 = torch.empty_like(k), torch.empty_like(k)
-        gK = torch.empty_like(K) if K is not None and need[2] else None
-        gv = torch.empty_like(v) if v is not None and need[3] else None
-        galpha = torch.empty_like(alpha) if alpha is not None and need[5] else None
-        glb = torch.empty_like(lb) if lb is not None and need[6] else None
-        gub = torch.empty_like(ub) if ub is not None and need[7] else None
-        if B > 0:
-            steps = T > 0  # without a step there is no log, no v and no gv to hand over
-            euler = ctx.plant == capi.PLANT_EULER
-            vjp = ctx.flt.rollout_params_vjp if euler else ctx.flt.rollout_plant_vjp
-            vjp(T, ctx.dt, *(() if euler else (ctx.plant,)), xlog, ulog, rclog, k, gxT, gx0, gk, guact0,
-                torch.empty(B, dtype=torch.int32, device=k.device), K=K, v=v if steps else None, alpha=alpha, lb=lb, ub=ub,
-                guactT=cont(guactT), gxlog=cont(gxlog) if steps else None, gulog=cont(gulog) if steps else None, gK=gK,
-                gv=gv if steps else None, galpha=galpha, glb=glb, gub=gub)
-        # one entry per forward argument, the optional integrator included (dropped where it was not passed)
-        return (None, gx0 if need[0] else None, gk if need[1] else None, gK, gv, guact0 if need[4] else None, galpha,
-                glb, gub, None, None, None)
+        return _policy_rollout_backward(ctx, gxT, guactT, gxlog, gulog)
 
 
-class ParamRolloutLayer(torch.nn.Module):
-    """Owns an explicit capi.Filter and rolls the closed loop out for T steps of dt under udes_t = k + K x_t + v_t with
-    the barrier gain and the input box per instance:
-    xT, uactT, xlog, ulog, rclog, nfail = layer(x0, k, K=None, v=None, uact_prev=None, alpha=None, lb=None, ub=None)."""
+class _PolicyRolloutLayer(torch.nn.Module):
+    """Owns an explicit capi.Filter and the rollout's T, dt and integrator."""
 
     def __init__(self, model=capi.MODEL_DOUBLE_INTEGRATOR, options=None, solver=None, device=0, T=1, dt=1e-3,
                  integrator="euler"):
@@ -380,6 +321,20 @@ class ParamRolloutLayer(torch.nn.Module):
         _plant(integrator)
         self.filter = capi.Filter(model, capi.EXPLICIT, options=options, solver=solver, device=device)
         self.T, self.dt, self.integrator = int(T), float(dt), integrator
+
+
+class PolicyRolloutLayer(_PolicyRolloutLayer):
+    """Owns an explicit capi.Filter and rolls the closed loop out for T steps of dt under udes_t = k + K x_t + v_t:
+    xT, uactT, xlog, ulog, rclog, nfail = layer(x0, k, K=None, v=None, uact_prev=None)."""
+
+    def forward(self, x0, k, K=None, v=None, uact_prev=None):
+        return PolicyRolloutFn.apply(self.filter, x0, k, K, v, uact_prev, self.T, self.dt, self.integrator)
+
+
+class ParamRolloutLayer(_PolicyRolloutLayer):
+    """Owns an explicit capi.Filter and rolls the closed loop out for T steps of dt under udes_t = k + K x_t + v_t with
+    the barrier gain and the input box per instance:
+    xT, uactT, xlog, ulog, rclog, nfail = layer(x0, k, K=None, v=None, uact_prev=None, alpha=None, lb=None, ub=None)."""
 
     def forward(self, x0, k, K=None, v=None, uact_prev=None, alpha=None, lb=None, ub=None):
         return ParamRolloutFn.apply(self.filter, x0, k, K, v, uact_prev, alpha, lb, ub, self.T, self.dt, self.integrator)
